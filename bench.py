@@ -49,6 +49,13 @@ size, the RCCL version, each rank's device index, PCI bus ID and UUID, and a dev
 distinct GPUs exits 3 before measuring anything, unless it is labelled a rehearsal (``DDL_REHEARSAL=1``:
 gloo ranks sharing one card, or CPU ranks); ``dist.rehearsal`` says which.
 
+A plain run (no ``--full``) is phase 1 alone: set up, W warmup steps, the K timed steps, the JSON line
+(``value``, ``ms_per_step`` = wall milliseconds of one timed step, max over ranks). ``--full`` adds everything
+else this file measures: the all-to-all probe of the ``dist`` block, phases 2 and 3 and the indexed order, each
+still switched by its own option. ``--dump-outputs DIR`` writes what the last timed step handed to the consumer
+(``batch_sample.npy``, ``batch_row_sums.npy``): producers, shuffle and sample positions are seeded, so two
+builds run with the same arguments can be compared array for array.
+
 vs_baseline = value / (28,500 samples/s x N): BASELINE.md's reference
 ceiling for this shape (P=3 host producers, f32, no H2D) scaled linearly.
 """
@@ -123,6 +130,16 @@ def parse(argv=None):
                     help="size of the device-timed all-to-all on the DP group that opens the run (the 'dist' block's "
                          "per-rank xGMI rate); 0 skips it")
     ap.add_argument("--json-out", default=None)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything next to the headline: the device-timed all-to-all probe of the 'dist' "
+                         "block, phase 2 (--idle-steps), phase 3 (--pressure-ratio) and the indexed order (--order). "
+                         "Without it a run sets up, warms up, times the --steps headline steps and prints its line; "
+                         "those options are then ignored")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step delivered to DIR as .npy files: "
+                         "batch_sample.npy (float32: the batch's elements at a fixed, seeded sample of positions; the "
+                         "whole batch when it is small) and batch_row_sums.npy (float64: every sample's sum over all "
+                         "of its elements). The same arguments give the same arrays in every run")
     ap.add_argument("--debug-log", action="store_true",
                     help="slow host iterations of the timed loop and long per-window stager waits in the JSON line")
     return ap.parse_args(argv)
@@ -516,6 +533,32 @@ def _pressure_sub(args, env, dev, it, feed_total: float, barrier, sync, dl=None)
     return {key: pr["gpu_idle_pct"], "pressure": pr}
 
 
+_DUMP_SAMPLE = 1 << 22  # elements of the last batch kept by --dump-outputs (16 MiB of float32)
+_DUMP_SEED = 20240607
+
+
+def _snapshot_outputs(x) -> dict:
+    """What ``--dump-outputs`` keeps of the batch ``x`` (taken while the batch's window is still held):
+    a fixed, seeded sample of its elements as float32 and every sample's sum as float64, on the host."""
+    import numpy as np
+    import torch
+
+    flat = x.reshape(-1)
+    if flat.numel() > _DUMP_SAMPLE:
+        idx = np.sort(np.random.default_rng(_DUMP_SEED).choice(flat.numel(), _DUMP_SAMPLE, replace=False))
+        flat = flat[torch.from_numpy(idx).to(flat.device)]
+    return {"batch_sample": flat.to(torch.float32).cpu().numpy(),
+            "batch_row_sums": x.reshape(x.shape[0], -1).sum(1, dtype=torch.float64).cpu().numpy()}
+
+
+def _write_outputs(dirname: str, arrays: dict, rank: int, world: int) -> None:
+    import numpy as np
+
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + (f"_rank{rank}" if world > 1 else "") + ".npy"), a)
+
+
 def _landed(dl) -> tuple[int, int]:
     st = getattr(dl, "_stager", None)
     if st is None:  # CPU rehearsal: the host path has no H2D; every delivered window counts
@@ -534,6 +577,8 @@ def main(argv=None) -> int:
         print(f"bench: --gpus {args.gpus} but WORLD_SIZE={os.environ['WORLD_SIZE']}; refusing to run",
               file=sys.stderr)
         return 2
+    if not args.full:  # a plain run is the headline alone: no all-to-all probe, no phase 2 / 3, no indexed order
+        args.a2a_probe_mb, args.idle_steps, args.pressure_ratio, args.order = 0.0, 0, 0.0, "window"
 
     import torch
     import torch.distributed as dist
@@ -660,6 +705,8 @@ def main(argv=None) -> int:
         else:
             n_in_prorata, b_in_prorata = float(n_in), float(b_in)
         prod1 = conn.producer_stats()
+        # the last timed batch, before the iterator moves on and its window is released for the next copy
+        dumped = _snapshot_outputs(x) if args.dump_outputs else None
         barrier()
         elapsed = t1 - t0
         landed_samples = n_in_prorata * args.window
@@ -770,6 +817,8 @@ def main(argv=None) -> int:
                 traceback.print_exc()
                 indexed = {"error": repr(e)[:300]}
 
+        if dumped is not None:
+            _write_outputs(args.dump_outputs, dumped, env.rank, env.world_size)
         if env.rank == 0:
             for r in per_rank:
                 for k in ("elapsed_s", "delivered_per_s", "landed_per_s", "h2d_gbps_timed"):
@@ -781,6 +830,7 @@ def main(argv=None) -> int:
                 "n_gpus": env.world_size,
                 "steps": args.steps,
                 "warmup": args.warmup,
+                "full": args.full,
                 "ms_per_step": round(1000.0 * elapsed / args.steps, 4),
                 "higher_is_better": True,
                 "scaling": "weak",

@@ -19,7 +19,7 @@ def main(argv=None) -> int:
     from ddl_amd.models.producers import ImageWindowProducer
 
     extra = list(sys.argv[1:] if argv is None else argv)  # e.g. --index-no-prefault
-    args = bench.parse(["--steps", "200", "--warmup", "20", "--idle-steps", "0", *extra])
+    args = bench.parse(["--full", "--steps", "200", "--warmup", "20", "--idle-steps", "0", *extra])
     res = {}
     with ddl_amd.start(n_producers=args.producers) as (env, conn):
         dev = torch.device(env.device)
@@ -45,7 +45,7 @@ def main(argv=None) -> int:
         dl.close()
         res["indexed_after_window_loader"] = bench.indexed_phase(args, env, dev, sync, sync)["value"]
     # bench.py's own window phase (its main, in this process), then the indexed phase again
-    bench.main(["--order", "window", "--idle-steps", "0"])
+    bench.main(["--full", "--order", "window", "--idle-steps", "0"])
     with ddl_amd.start(n_producers=args.producers) as (env, conn):
         dev = torch.device(env.device)
         res["indexed_after_bench_main"] = bench.indexed_phase(args, env, dev, sync, sync)["value"]

@@ -19,7 +19,7 @@ def test_bench_n1_reports_pressure_idle():
     env = {k: v for k, v in os.environ.items()
            if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "DDL_BACKEND", "MASTER_PORT")}
     env["PYTHONPATH"] = REPO
-    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "20", "--warmup", "5",
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--full", "--steps", "20", "--warmup", "5",
                         "--order", "window"], capture_output=True, text=True, timeout=180, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
@@ -39,7 +39,7 @@ def test_bench_one_rank_rccl_prints_dist_block():
     env = {k: v for k, v in os.environ.items()
            if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "DDL_REHEARSAL")}
     env.update(PYTHONPATH=REPO, DDL_BACKEND="nccl")
-    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "20", "--warmup", "5",
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--full", "--steps", "20", "--warmup", "5",
                         "--order", "window", "--exchange", "0.5", "--pressure-ratio", "0", "--idle-steps", "0"],
                        capture_output=True, text=True, timeout=180, env=env)
     assert r.returncode == 0, r.stderr[-3000:]

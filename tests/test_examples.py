@@ -45,7 +45,7 @@ def test_bench_contract_two_ranks_torchrun():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(free_port()), os.path.join(REPO, "bench.py"),
            "--gpus", "2", "--steps", "6", "--warmup", "2", "--window", "64", "--batch", "16", "--idle-steps", "3",
-           "--model-dim", "64", "--model-depth", "1"]
+           "--model-dim", "64", "--model-depth", "1", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=280,
                        env=dict(_env(), DDL_DEVICE="cpu", DDL_REHEARSAL="1"))
     assert r.returncode == 0, r.stderr[-3000:]
@@ -61,6 +61,39 @@ def test_bench_contract_two_ranks_torchrun():
     assert "DDP" in out["train_step"]["model"]
 
 
+@pytest.mark.timeout(200)
+def test_bench_plain_run_is_the_headline_alone_and_dumps_its_outputs(tmp_path):
+    """Without ``--full`` a run is phase 1 only, whatever the phase options say, and ``--dump-outputs`` writes
+    the last timed batch (a float32 element sample, float64 per-sample sums): the same arrays in two runs."""
+    import json
+
+    import numpy as np
+
+    outs = []
+    for d in ("a", "b"):
+        cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2",
+               "--window", "32", "--batch", "16", "--idle-steps", "3", "--dump-outputs", str(tmp_path / d)]
+        env = {k: v for k, v in _env().items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=90, env=dict(env, DDL_DEVICE="cpu"))
+        assert r.returncode == 0, r.stderr[-3000:]
+        (line,) = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        outs.append(json.loads(line))
+    out = outs[0]
+    assert out["full"] is False and out["steps"] == 5 and out["warmup"] == 2 and out["value"] > 0
+    # the region's wall time over its 5 steps; elapsed_s is printed rounded to 1e-4 s, i.e. to 0.01 ms per step
+    assert out["ms_per_step"] == pytest.approx(1000.0 * out["per_rank"][0]["elapsed_s"] / 5, abs=0.0101)
+    assert out["gpu_idle_pct"] is None and out["train_step"] is None and out["pressure"] is None
+    assert out["indexed"] is None and "alltoall" not in out["dist"]["ranks"][0]
+    assert sorted(os.listdir(tmp_path / "a")) == ["batch_row_sums.npy", "batch_sample.npy"]
+    sample, sums = np.load(tmp_path / "a" / "batch_sample.npy"), np.load(tmp_path / "a" / "batch_row_sums.npy")
+    assert sample.dtype == np.float32 and sample.shape == (16 * 3 * 224 * 224,)  # small enough: the whole batch
+    assert sums.dtype == np.float64 and sums.shape == (16,)
+    # float64 sums of 150,528 non-negative terms in another order: apart by at most n * 2^-53 = 1.7e-11 relative
+    np.testing.assert_allclose(sample.reshape(16, -1).sum(1, dtype=np.float64), sums, rtol=1e-10)
+    assert np.array_equal(sample, np.load(tmp_path / "b" / "batch_sample.npy"))
+    assert np.array_equal(sums, np.load(tmp_path / "b" / "batch_row_sums.npy"))
+
+
 @pytest.mark.timeout(300)
 @pytest.mark.parametrize("method,launch", [("alltoall", "torchrun"), ("sendrecv_replace", "self")])
 def test_bench_eight_ranks(method, launch):
@@ -73,7 +106,7 @@ def test_bench_eight_ranks(method, launch):
 
     args = [os.path.join(REPO, "bench.py"), "--gpus", "8", "--steps", "12", "--warmup", "2", "--window", "64",
             "--batch", "16", "--idle-steps", "3", "--model-dim", "64", "--model-depth", "1",
-            "--exchange-method", method]
+            "--exchange-method", method, "--full"]
     if launch == "torchrun":
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8",
                "--master-addr", "127.0.0.1", "--master-port", str(free_port()), *args]

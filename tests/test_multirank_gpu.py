@@ -82,7 +82,7 @@ def test_exchange_conserves_rows_on_device(world, slow):
 
 def _run_bench(n, launch, extra=()):
     args = [os.path.join(REPO, "bench.py"), "--gpus", str(n), "--steps", "24", "--warmup", "6",
-            "--idle-steps", "6", *extra]
+            "--idle-steps", "6", "--full", *extra]
     env = dict(os.environ, PYTHONPATH=REPO, **GPU_GLOO)
     if launch == "torchrun":
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n),

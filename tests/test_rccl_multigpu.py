@@ -40,7 +40,7 @@ def test_bench_line_verifies_rccl_over_distinct_gpus():
     """The driver's command at N = all GPUs of the node: RCCL over N distinct PCI bus IDs, a device-timed
     all-to-all on the DP group, one collective order, and every rank fed."""
     out = _torchrun(N_GPUS, "bench.py", "--gpus", str(N_GPUS), "--steps", "20", "--warmup", "5",
-                    "--order", "window", "--pressure-ratio", "0")
+                    "--order", "window", "--pressure-ratio", "0", "--full")
     d = out["dist"]
     assert d["backend"] == "nccl" and d["group_size"] == N_GPUS and d["verified"] is True and not d["problems"]
     assert d["distinct_gpus"] == N_GPUS and len({r["pci_bus_id"] for r in d["ranks"]}) == N_GPUS

@@ -2,10 +2,10 @@
 """GPU idle % from a rocprofv3 trace: the cross-check of ``ComputeIdleMeter``.
 
 ``bench.py`` brackets its timed regions with roctx ranges ``bench.phase1`` /
-``bench.phase2``. Run it under
+``bench.phase2`` (phase 2 runs with ``--full`` only). Run it under
 
     rocprofv3 --kernel-trace --memory-copy-trace --marker-trace --output-format csv \
-        -d gpurun_out/trace -o bench -- python3 bench.py ...
+        -d trace -o bench -- python3 bench.py --full ...
 
 and this tool reads the CSVs, clips every kernel dispatch and every copy to a
 marked region and reports:
