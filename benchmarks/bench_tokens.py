@@ -45,7 +45,13 @@ def main(argv=None):
                     help="token ids in the corpus and on the wire: auto = uint16 when every id is < 65536 (the "
                          "synthetic GPT-2-sized vocabulary is), else int32; uint16 ships 2 B per token over PCIe "
                          "and the pack kernel widens it to int32 input_ids (archive/profiles/r3_tok16)")
+    ap.add_argument("--path", default="producers", choices=["producers", "zerocopy"],
+                    help="producers: host producers gather into pinned windows (TokenBatchProducer); zerocopy: the "
+                         "ragged gather kernel reads the registered corpus over PCIe (ZeroCopyTokenLoader)")
+    ap.add_argument("--max-blocks", type=int, default=None,
+                    help="zerocopy: grid cap of the gather kernel (0 = uncapped; default: the loader's)")
     a = ap.parse_args(argv)
+    zc = a.path == "zerocopy"
 
     import torch
     import torch.distributed as dist
@@ -69,7 +75,7 @@ def main(argv=None):
         tb_seg.tensor().view(-1)[0] = src.token_bytes
     gb = a.batch * world
     try:
-        with ddl_amd.start(n_producers=a.producers) as (env, conn):
+        with ddl_amd.start(n_producers=0 if zc else a.producers) as (env, conn):
             if env.world_size > 1:
                 dist.barrier(group=env.control_group)
             if src is None:
@@ -87,15 +93,20 @@ def main(argv=None):
             else:
                 source = src
             n_epochs = (a.warmup + a.steps + a.idle_steps + a.warmup // 2) // (a.n_seqs // gb) + 2
-            producer = TokenBatchProducer(source, gb, a.seq_len, a.mode,
-                                          pack_order=a.pack_order if a.mode == "pack" else "in_order",
-                                          batches_per_window=a.batches_per_window, host_threads=a.host_threads)
-            dispatch = False if a.dispatch == "python" else a.dispatch
-            dl = ddl_amd.DistributedDataLoader(producer, a.batch, conn, n_epochs, env=env, auto_mark=True,
-                                               output=ddl_amd.OutputSpec(collate="tokens", token_rows=a.token_rows),
-                                               staging=ddl_amd.StagingSpec(n_slots=a.slots,
-                                                                           native_dispatch=dispatch),
-                                               order=ddl_amd.OrderSpec(mode="indexed"))
+            pack_order = a.pack_order if a.mode == "pack" else "in_order"
+            if zc:
+                dl = ddl_amd.ZeroCopyTokenLoader(source, gb, a.seq_len, a.mode, env, pack_order=pack_order,
+                                                 token_rows=a.token_rows, max_blocks=a.max_blocks, n_epochs=n_epochs)
+            else:
+                producer = TokenBatchProducer(source, gb, a.seq_len, a.mode, pack_order=pack_order,
+                                              batches_per_window=a.batches_per_window, host_threads=a.host_threads)
+                dispatch = False if a.dispatch == "python" else a.dispatch
+                dl = ddl_amd.DistributedDataLoader(producer, a.batch, conn, n_epochs, env=env, auto_mark=True,
+                                                   output=ddl_amd.OutputSpec(collate="tokens",
+                                                                             token_rows=a.token_rows),
+                                                   staging=ddl_amd.StagingSpec(n_slots=a.slots,
+                                                                               native_dispatch=dispatch),
+                                                   order=ddl_amd.OrderSpec(mode="indexed"))
             dev = torch.device(env.device)
             acc = ops.ChecksumAccumulator(dev)  # one streaming launch per batch
 
@@ -162,9 +173,25 @@ def main(argv=None):
                 t = torch.tensor([real], dtype=torch.float64)
                 dist.all_reduce(t, group=env.control_group)
                 real_tokens = float(t.item())
+            bpw = None if zc else dl.batches_per_window[0]
             dl.close()
             if env.rank == 0:
-                print(json.dumps({
+                if zc:
+                    per_path = {"path": "zerocopy", "max_blocks": st["max_blocks"], "host_waits": st["host_waits"],
+                                "prefault_s": round(st["prefault_s"], 3)}
+                else:
+                    per_path = {
+                        "producers": a.producers, "host_threads": a.host_threads, "slots": a.slots,
+                        "batches_per_window": bpw, "dispatch": a.dispatch,
+                        "dispatch_mode": (st.get("native_dispatch") or {}).get("mode"),
+                        "consumer_wait_s": round(st["consumer_wait_s"], 3),
+                        "stager_wait_producer_s": round(st.get("stager_wait_producer_s", 0.0), 3),
+                        # per producer: rounds, mean fill and mean slot-wait per round (us) -- where the feed goes
+                        "producers_rounds_fill_wait_us": [
+                            (p["rounds"], round(p["fill_ns_total"] / max(1, p["rounds"]) / 1e3, 1),
+                             round(p["wait_ns_total"] / max(1, p["rounds"]) / 1e3, 1))
+                            for p in st.get("producers", [])]}
+                res = {
                     "metric": "tokens/s fed to GPU (seq_len 4096, on-device pad/pack)", "mode": a.mode,
                     "value": round(real_tokens / dt, 1), "unit": "tokens/s (real tokens delivered)",
                     "value_est_from_mean_len": round(est_tokens / dt, 1),
@@ -175,24 +202,17 @@ def main(argv=None):
                     "row_density_est": round(a.batch * mean_len / (rows / a.steps) / a.seq_len, 3),
                     "n_gpus": env.world_size,
                     "steps": a.steps, "ms_per_step": round(1000 * dt / a.steps, 3), "batch_seqs": a.batch,
-                    "producers": a.producers, "host_threads": a.host_threads, "slots": a.slots,
-                    "batches_per_window": dl.batches_per_window[0], "dispatch": a.dispatch,
-                    "dispatch_mode": (st.get("native_dispatch") or {}).get("mode"), "token_rows": a.token_rows,
+                    "token_rows": a.token_rows,
                     "mean_len": round(mean_len, 1),
                     "token_wire_dtype": "uint16" if source.token_bytes == 2 else "int32",
                     "h2d_token_gbps": round(real_tokens * source.token_bytes / dt / 1e9, 2),
-                    "consumer_wait_s": round(st["consumer_wait_s"], 3),
-                    "stager_wait_producer_s": round(st.get("stager_wait_producer_s", 0.0), 3),
-                    # per producer: rounds, mean fill and mean slot-wait per round (us) -- where the feed goes
-                    "producers_rounds_fill_wait_us": [
-                        (p["rounds"], round(p["fill_ns_total"] / max(1, p["rounds"]) / 1e3, 1),
-                         round(p["wait_ns_total"] / max(1, p["rounds"]) / 1e3, 1)) for p in st.get("producers", [])],
+                    **per_path,
                     "gpu_idle_pct": None if idle is None else round(idle["gpu_idle_pct"], 3),
                     "train_step": None if idle is None else {
                         "model": f"TokenMLP dim={a.model_dim} depth={a.model_depth} fwd+bwd+SGD bf16",
                         "sequences_per_s": round(idle["train_sequences_per_s"], 1),
-                        "busy_ms": round(idle["busy_ms"], 3), "wall_ms": round(idle["wall_ms"], 3)}}),
-                    flush=True)
+                        "busy_ms": round(idle["busy_ms"], 3), "wall_ms": round(idle["wall_ms"], 3)}}
+                print(json.dumps(res), flush=True)
     finally:
         if src is not None:
             src.close()

@@ -23,6 +23,7 @@
 
 #include "common.h"
 #include "launch.h"
+#include "ragged_index.h"
 #include "engine.h"
 #include "stager.h"
 
@@ -733,7 +734,32 @@ PYBIND11_MODULE(_ddl_hip, m) {
       py::arg("segment_ids"), py::arg("cu_seqlens_out"), py::arg("rows"), py::arg("seq_len"), py::arg("pad_id"),
       py::arg("mode"), py::arg("stream"), py::arg("fill_rows") = 0, py::arg("dev_counts") = 0,
       py::arg("tok16") = false);
-  m.def("pack_plan_scratch_ints", &ddl::pack_plan_scratch_ints, py::arg("max_segs"), py::arg("max_rows"));
+  m.attr("RAGGED_MAP_CAP") = ddl::kRaggedMapCap;
+  m.def(
+      "ragged_tile_plan",
+      [](uintptr_t src, uintptr_t src_start, uintptr_t dst_offsets, int64_t n, int elem_bytes, uintptr_t tile_start) {
+        if (elem_bytes != 2 && elem_bytes != 4) throw std::invalid_argument("ragged_tile_plan: 2- or 4-byte elements");
+        const int64_t t = ddl::ragged_tile_plan(src, as_ptr<const int64_t>(src_start),
+                                                as_ptr<const int64_t>(dst_offsets), n, elem_bytes,
+                                                as_ptr<int32_t>(tile_start));
+        if (t < 0) throw std::overflow_error("ragged_tile_plan: more than 2^31 tiles");
+        return t;
+      },
+      py::arg("src"), py::arg("src_start"), py::arg("dst_offsets"), py::arg("n"), py::arg("elem_bytes"),
+      py::arg("tile_start"),
+      "host: tile_start[0..n] (int32) of a ragged gather whose source is at device address src; returns the tiles");
+  m.def(
+      "gather_ragged",
+      [](uintptr_t dst, uintptr_t src, uintptr_t src_start, uintptr_t dst_offsets, uintptr_t tile_start, int64_t n,
+         int64_t n_tiles, int elem_bytes, int64_t max_blocks, uintptr_t stream) {
+        check_rc(ddl::gather_ragged(as_ptr<void>(dst), as_ptr<const void>(src), as_ptr<const int64_t>(src_start),
+                                    as_ptr<const int64_t>(dst_offsets), as_ptr<const int32_t>(tile_start), n, n_tiles,
+                                    elem_bytes, max_blocks, as_stream(stream)),
+                 "gather_ragged");
+      },
+      py::arg("dst"), py::arg("src"), py::arg("src_start"), py::arg("dst_offsets"), py::arg("tile_start"), py::arg("n"),
+      py::arg("n_tiles"), py::arg("elem_bytes"), py::arg("max_blocks"), py::arg("stream"));
+  m.def("pack_plan_scratch_ints",&ddl::pack_plan_scratch_ints, py::arg("max_segs"), py::arg("max_rows"));
   m.def(
       "pack_plan_device",
       [](uintptr_t offsets, int64_t n, int64_t seq_len, int64_t max_segs, int64_t max_rows, uintptr_t seg_offsets,

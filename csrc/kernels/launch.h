@@ -129,6 +129,18 @@ int pack_plan_device(const PackPlanSpec& spec, hipStream_t st);
 constexpr int kMaxTokenSubs = 16;
 int pad_pack_tokens_multi(const TokenSpec* specs, int n, hipStream_t st);
 
+// ragged.hip ----------------------------------------------------------------
+// Device twin of the host gather_ragged: sequence i (src_start[i] elements into src, dst_offsets[i + 1] -
+// dst_offsets[i] elements of elem_bytes = 2 or 4) -> dst[dst_offsets[i] ...). src: HBM or pinned,
+// device-mapped host memory (16-byte aligned non-temporal loads of each sequence's aligned hull; nothing
+// outside the hulls is read); dst: HBM. tile_start[n + 1] / n_tiles: the tile map of ragged_index.h
+// (ragged_tile_plan, host-built); the three arrays are device-readable. max_blocks > 0 caps the grid.
+// n == 0 or n_tiles == 0 launches nothing.
+constexpr int kRaggedMapCap = 2047;  // sequences whose tile map (n + 1 int32) is searched in LDS
+int gather_ragged(void* dst, const void* src, const int64_t* src_start, const int64_t* dst_offsets,
+                  const int32_t* tile_start, int64_t n, int64_t n_tiles, int elem_bytes, int64_t max_blocks,
+                  hipStream_t st);
+
 // bucket.hip ----------------------------------------------------------------
 // Owner bucketing of a global batch for the resident loader's exchange: positions
 // [pos0, pos0 + count) of the Feistel permutation `keys`, sample idx owned by rank

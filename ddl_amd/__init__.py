@@ -19,6 +19,7 @@ __all__ = [
     "FeistelPermutation",
     "EpochOrder",
     "IndexedProducer",
+    "ZeroCopyTokenLoader",
     "DataLoader",
     "OutputSpec",
     "StagingSpec",
@@ -41,6 +42,10 @@ def __getattr__(name):
         from .models.producers import IndexedProducer
 
         return IndexedProducer
+    if name == "ZeroCopyTokenLoader":
+        from .zerocopy_tokens import ZeroCopyTokenLoader
+
+        return ZeroCopyTokenLoader
     if name == "DataLoader":
         from .frontend import DataLoader
 

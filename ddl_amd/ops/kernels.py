@@ -232,6 +232,71 @@ def cast(x: torch.Tensor, dtype, *, scale=None, bias=None, plane=None, stream=No
     return out.reshape(x.shape)
 
 
+# -------------------------------------------------------------- ragged gather
+def _ragged_args(src, src_offsets, idx) -> tuple[torch.Tensor, np.ndarray, np.ndarray]:
+    """Checked (flat source tensor, src_start [n], dst_offsets [n + 1]) of a ragged gather."""
+    flat = (src.cpu if isinstance(src, HostRows) else src).reshape(-1)
+    if flat.element_size() not in (2, 4):
+        raise TypeError("gather_ragged: 2- or 4-byte elements")
+    offs = np.ascontiguousarray(src_offsets.numpy() if isinstance(src_offsets, torch.Tensor) else src_offsets,
+                                dtype=np.int64).reshape(-1)
+    idx = np.ascontiguousarray(idx.numpy() if isinstance(idx, torch.Tensor) else idx, dtype=np.int64).reshape(-1)
+    if offs.size < 1 or (idx.size and (idx.min() < 0 or idx.max() >= offs.size - 1)):
+        raise IndexError("gather_ragged: sequence index out of range")
+    start, lens = offs[idx], offs[idx + 1] - offs[idx]
+    if idx.size and (lens.min() < 0 or start.min() < 0 or (start + lens).max() > flat.numel()):
+        raise ValueError("gather_ragged: source offsets decrease or run past the source")
+    return flat, start, np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+
+
+def ref_gather_ragged(src, src_offsets, idx) -> tuple[torch.Tensor, torch.Tensor]:
+    """(tokens, offsets): sequences ``idx`` of the flat ``src`` (sequence i = src[src_offsets[i]:src_offsets[i+1]])
+    back to back, and their int64 running offsets [n + 1]."""
+    flat, start, dofs = _ragged_args(src, src_offsets, idx)
+    flat = flat.cpu()
+    parts = [flat[s:s + n] for s, n in zip(start.tolist(), np.diff(dofs).tolist())]
+    return (torch.cat(parts) if parts else flat[:0].clone()), torch.from_numpy(dofs)
+
+
+def gather_ragged(src, src_offsets, idx, *, out: torch.Tensor | None = None, max_blocks: int = 0,
+                  stream=None) -> tuple[torch.Tensor, torch.Tensor]:
+    """Ragged gather on the device: ``src`` is a flat device tensor or ``HostRows`` (pinned, device-mapped host
+    memory: every token crosses PCIe once, in 16-byte aligned loads); ``src_offsets`` and ``idx`` live on the
+    host. Returns (tokens [sum of lengths] in ``out`` if given, offsets [n + 1] int64), both on the device.
+    ``max_blocks`` > 0 caps the grid as for ``gather_rows``."""
+    if not _is_gpu(src):
+        tokens, dofs = ref_gather_ragged(src, src_offsets, idx)
+        if out is not None:
+            out.reshape(-1)[:tokens.numel()].copy_(tokens)
+            return out.reshape(-1)[:tokens.numel()], dofs
+        return tokens, dofs
+    flat, start, dofs = _ragged_args(src, src_offsets, idx)
+    if isinstance(src, torch.Tensor) and not src.is_contiguous():
+        raise ValueError("gather_ragged: source must be contiguous")
+    n, total, eb = int(start.size), int(dofs[-1]), flat.element_size()
+    # one descriptor: src_start [n] i64, dst_offsets [n + 1] i64, tile_start [n + 1] i32
+    words = np.zeros(2 * n + 1 + (n + 2) // 2, dtype=np.int64)
+    words[:n], words[n:2 * n + 1] = start, dofs
+    hip, addr = _native.hip(), _src_addr(src)
+    n_tiles = hip.ragged_tile_plan(addr, words.ctypes.data, words[n:].ctypes.data, n, eb,
+                                   words[2 * n + 1:].ctypes.data)
+    dev = src.device
+    if out is None:
+        out = torch.empty(total, dtype=flat.dtype, device=dev)
+    elif not out.is_cuda or not out.is_contiguous() or out.dtype != flat.dtype or out.numel() < total:
+        raise ValueError("gather_ragged: bad out tensor")
+    handle = _stream_handle(stream)
+    if isinstance(stream, int):
+        stream = torch.cuda.ExternalStream(stream, device=dev)
+    with torch.cuda.stream(stream):  # None: the current stream. The descriptor is allocated and copied on it
+        desc = torch.from_numpy(words).to(dev)  # a pageable copy: complete for the host on return
+    base = desc.data_ptr()
+    hip.gather_ragged(dst=out.data_ptr(), src=addr, src_start=base, dst_offsets=base + 8 * n,
+                      tile_start=base + 8 * (2 * n + 1), n=n, n_tiles=n_tiles, elem_bytes=eb,
+                      max_blocks=int(max_blocks), stream=handle)
+    return out.reshape(-1)[:total], desc[n:2 * n + 1]
+
+
 # -------------------------------------------------------------------- collate
 def ref_collate_hwc_to_chw(src, index=None, perm=None, base=0, n_rows=None, out_dtype=torch.bfloat16, mean=None,
                            std=None, scale=None, bias=None) -> torch.Tensor:

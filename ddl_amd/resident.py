@@ -145,8 +145,17 @@ class PrefetchedIndexedLoader:
         blk[1] += n
         return out
 
-    def _record_caller(self, batch: torch.Tensor, cur) -> None:
-        """``record_stream`` of the caller's stream on the batch's block (once per block and stream)."""
+    def _record_caller(self, batch, cur) -> None:
+        """``record_stream`` of the caller's stream on the batch's block (once per block and stream). A dict
+        batch (token loaders) holds allocations of its own made on the prep stream: the caller's stream is
+        recorded on each of them (once per storage)."""
+        if isinstance(batch, dict):
+            seen = set()
+            for v in batch.values():
+                if isinstance(v, torch.Tensor) and v.is_cuda and v.untyped_storage().data_ptr() not in seen:
+                    seen.add(v.untyped_storage().data_ptr())
+                    v.record_stream(cur)
+            return
         base = batch._base if batch._base is not None else batch
         rec = self._rec
         if rec[0] is not base:

@@ -39,6 +39,65 @@ from .utils import streams
 _PAGE = 4096
 
 
+_SHARED_REGS: dict[int, list] = {}  # page-rounded base -> [bytes, users, registered by this process]
+
+
+def register_mapping(addr: int, nbytes: int, shared: bool = False) -> tuple[int | None, int]:
+    """Register the page-rounded range of a shm segment / file mapping at ``addr`` (the rounded range is the
+    mapping itself) as pinned, device-mapped memory. Returns (handle for ``unregister_mapping``, device address
+    of ``addr``). ``shared``: loaders over the same mapping (train + eval over one corpus) share one
+    registration, counted per process, and a range that something else registered is used as it is and never
+    unregistered here; the handle is then the base as well, and the last ``unregister_mapping`` unregisters."""
+    hip = _native.hip()
+    base = addr & ~(_PAGE - 1)
+    size = -(-(addr + nbytes - base) // _PAGE) * _PAGE
+    if not shared:
+        hip.host_register(base, size, True)
+        return base, hip.host_device_pointer(base) + (addr - base)
+    reg = _SHARED_REGS.get(base)
+    if reg is None:
+        foreign = hip.pointer_is_host_registered(base)
+        if not foreign:
+            hip.host_register(base, size, True)
+        reg = _SHARED_REGS[base] = [size, 0, not foreign]
+    elif reg[0] < size:
+        raise ValueError("a shorter range of this mapping is already registered")
+    reg[1] += 1
+    return base, hip.host_device_pointer(base) + (addr - base)
+
+
+def unregister_mapping(base: int, device, shared: bool = False) -> None:
+    """Give back a ``register_mapping`` handle: the device is synchronised before the range is unregistered
+    (by the last user, if shared and registered here)."""
+    if shared:
+        reg = _SHARED_REGS[base]
+        reg[1] -= 1
+        if reg[1] > 0:
+            return
+        del _SHARED_REGS[base]
+        if not reg[2]:
+            return
+    torch.cuda.synchronize(device)
+    _native.hip().host_unregister(base)
+
+
+def prefault_mapping(dptr: int, nbytes: int, device, stream) -> float:
+    """Read one word of every 4 KB page of the mapped source once, before the first batch: the first
+    pass of zero-copy gathers over never-touched mapped pages ran ~14% slower than every later pass
+    (archive/profiles/r3_s2_final2). Returns the seconds it took (one small kernel, synchronised)."""
+    import time
+
+    if nbytes < 4:
+        return 0.0
+    t0 = time.perf_counter()
+    blocks = 256
+    sink = torch.empty(blocks, dtype=torch.int32, device=device)
+    with streams.on_stream(stream):
+        _native.hip().touch_pages(dptr, nbytes, _PAGE, sink.data_ptr(), blocks, stream.cuda_stream)
+    stream.synchronize()
+    return time.perf_counter() - t0
+
+
 def _cpu_view(source, n: int, shape, dtype) -> torch.Tensor:
     if isinstance(source, torch.Tensor):
         return source
@@ -101,11 +160,7 @@ class ZeroCopyLoader(PrefetchedIndexedLoader):
                 dptr = hip.host_device_pointer(self.cpu.data_ptr())
             else:
                 # shm segments / file mappings: the rounded range is the mapping itself
-                base = addr & ~(_PAGE - 1)
-                size = -(-(addr + self.nbytes - base) // _PAGE) * _PAGE
-                hip.host_register(base, size, True)
-                self._reg_base = base
-                dptr = hip.host_device_pointer(base) + (addr - base)
+                self._reg_base, dptr = register_mapping(addr, self.nbytes)
             self.rows = ops.HostRows(self.cpu, dptr)
             self.prep_stream = streams.batch_stream(self.device)
             # prep_streams = 2: consecutive batches' gathers alternate between two streams, so the next one
@@ -119,21 +174,7 @@ class ZeroCopyLoader(PrefetchedIndexedLoader):
             self.rows = self.cpu
 
     def _prefault(self, dptr: int) -> float:
-        """Read one word of every 4 KB page of the mapped source once, before the first batch: the first
-        pass of zero-copy gathers over never-touched mapped pages ran ~14% slower than every later pass
-        (archive/profiles/r3_s2_final2). Returns the seconds it took (one small kernel, synchronised)."""
-        import time
-
-        if self.nbytes < 4:
-            return 0.0
-        t0 = time.perf_counter()
-        blocks = 256
-        sink = torch.empty(blocks, dtype=torch.int32, device=self.device)
-        with streams.on_stream(self.prep_stream):
-            _native.hip().touch_pages(dptr, self.nbytes, _PAGE, sink.data_ptr(), blocks,
-                                      self.prep_stream.cuda_stream)
-        self.prep_stream.synchronize()
-        return time.perf_counter() - t0
+        return prefault_mapping(dptr, self.nbytes, self.device, self.prep_stream)
 
     def _assemble(self, t: int):
         e, g = divmod(t, self.order.batches_per_epoch)
@@ -164,8 +205,7 @@ class ZeroCopyLoader(PrefetchedIndexedLoader):
         self._queue.clear()
         self._blk, self._rec = None, [None, set()]
         if self._reg_base is not None:
-            torch.cuda.synchronize(self.device)
-            _native.hip().host_unregister(self._reg_base)
+            unregister_mapping(self._reg_base, self.device)
             self._reg_base = None
 
     def __del__(self):  # pragma: no cover - best effort

@@ -20,6 +20,10 @@ batch on the GPU with the pad/pack kernel:
 ``batches_per_window=k`` ships k consecutive global batches per producer window
 (one producer round, one H2D copy and one stager hand-off per k batches).
 
+``--zero-copy`` needs no producers: ``ZeroCopyTokenLoader`` registers the corpus once and a gfx950 kernel
+gathers each batch's ragged sequences straight out of it over PCIe (no host copy; every token is read from
+DRAM once). Same batches, same checkpoint.
+
 ``state_dict()`` is the indexed-kind cursor (seed, epoch, global batch), so a
 job can resume at another world size.
 """
@@ -41,13 +45,15 @@ def main() -> None:
     ap.add_argument("--global-batch", type=int, default=32, help="sequences per global step")
     ap.add_argument("--epochs", type=int, default=2)
     ap.add_argument("--batches-per-window", type=int, default=4)
+    ap.add_argument("--zero-copy", action="store_true",
+                    help="no producers: the GPU gathers the batches out of the registered corpus")
     a = ap.parse_args()
 
     name = f"ddl_amd_example_tok_{os.environ.get('MASTER_PORT', os.getpid())}"
     creator = int(os.environ.get("LOCAL_RANK", "0")) == 0
     src = SharedTokenSource.synthetic(name, a.n_seqs, 64, a.seq_len, seed=0) if creator else None
     try:
-        with ddl_amd.start(n_producers=2) as (env, conn):
+        with ddl_amd.start(n_producers=0 if a.zero_copy else 2) as (env, conn):
             if env.world_size > 1:
                 torch.distributed.barrier(group=env.control_group)
             if src is None:  # other local ranks attach to the creator's segments
@@ -56,12 +62,16 @@ def main() -> None:
                 offs = SharedArraySource(name + "_off", a.n_seqs + 1, (1,), "int64")
                 n_tok = int(offs.tensor()[-1])
                 src = SharedTokenSource(SharedArraySource(name + "_tok", n_tok, (1,), "int32"), offs, a.seq_len)
-            producer = TokenBatchProducer(src, a.global_batch, a.seq_len, a.mode,
-                                          pack_order="ffd" if a.mode == "pack" else "in_order",
-                                          batches_per_window=a.batches_per_window)
-            dl = ddl_amd.DistributedDataLoader(producer, a.global_batch // env.world_size, conn, a.epochs, env=env,
-                                               order=ddl_amd.OrderSpec(mode="indexed"),
-                                               output=ddl_amd.OutputSpec(collate="tokens"), auto_mark=True)
+            pack_order = "ffd" if a.mode == "pack" else "in_order"
+            if a.zero_copy:
+                dl = ddl_amd.ZeroCopyTokenLoader(src, a.global_batch, a.seq_len, a.mode, env, pack_order=pack_order,
+                                                 n_epochs=a.epochs)
+            else:
+                producer = TokenBatchProducer(src, a.global_batch, a.seq_len, a.mode, pack_order=pack_order,
+                                              batches_per_window=a.batches_per_window)
+                dl = ddl_amd.DistributedDataLoader(producer, a.global_batch // env.world_size, conn, a.epochs,
+                                                   env=env, order=ddl_amd.OrderSpec(mode="indexed"),
+                                                   output=ddl_amd.OutputSpec(collate="tokens"), auto_mark=True)
             for epoch in range(a.epochs):
                 real = rows = 0
                 for b in dl:
@@ -75,6 +85,8 @@ def main() -> None:
                     print(f"epoch {epoch}: {rows} rows x {a.seq_len} on rank 0, {real} real tokens "
                           f"({100.0 * real / max(rows * a.seq_len, 1):.1f}% dense){extra}; keys {sorted(b)}",
                           flush=True)
+            if a.zero_copy:
+                dl.close()
     finally:
         if src is not None:
             src.close()
