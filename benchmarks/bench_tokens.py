@@ -45,13 +45,18 @@ def main(argv=None):
                     help="token ids in the corpus and on the wire: auto = uint16 when every id is < 65536 (the "
                          "synthetic GPT-2-sized vocabulary is), else int32; uint16 ships 2 B per token over PCIe "
                          "and the pack kernel widens it to int32 input_ids (archive/profiles/r3_tok16)")
-    ap.add_argument("--path", default="producers", choices=["producers", "zerocopy"],
+    ap.add_argument("--path", default="producers", choices=["producers", "zerocopy", "resident"],
                     help="producers: host producers gather into pinned windows (TokenBatchProducer); zerocopy: the "
-                         "ragged gather kernel reads the registered corpus over PCIe (ZeroCopyTokenLoader)")
+                         "ragged gather kernel reads the registered corpus over PCIe (ZeroCopyTokenLoader); resident: "
+                         "the corpus is copied into HBM once and one kernel packs every batch out of it "
+                         "(ResidentTokenLoader; also reports host_us_per_step and kernel_us)")
+    ap.add_argument("--kernel-sample", type=int, default=16,
+                    help="resident: device events around the pack launch of every N-th step (kernel_us; 0 = none)")
     ap.add_argument("--max-blocks", type=int, default=None,
                     help="zerocopy: grid cap of the gather kernel (0 = uncapped; default: the loader's)")
     a = ap.parse_args(argv)
-    zc = a.path == "zerocopy"
+    zc = a.path in ("zerocopy", "resident")  # producer-free paths
+    resident = a.path == "resident"
 
     import torch
     import torch.distributed as dist
@@ -94,7 +99,11 @@ def main(argv=None):
                 source = src
             n_epochs = (a.warmup + a.steps + a.idle_steps + a.warmup // 2) // (a.n_seqs // gb) + 2
             pack_order = a.pack_order if a.mode == "pack" else "in_order"
-            if zc:
+            if resident:
+                dl = ddl_amd.ResidentTokenLoader(source, gb, a.seq_len, a.mode, env, pack_order=pack_order,
+                                                 token_rows=a.token_rows, n_epochs=n_epochs)
+                dl.profile_every = a.kernel_sample
+            elif zc:
                 dl = ddl_amd.ZeroCopyTokenLoader(source, gb, a.seq_len, a.mode, env, pack_order=pack_order,
                                                  token_rows=a.token_rows, max_blocks=a.max_blocks, n_epochs=n_epochs)
             else:
@@ -136,6 +145,9 @@ def main(argv=None):
             sync()
             dt = time.perf_counter() - t0
             st = dl.stats()
+            timing = dl.timing() if resident else None  # of the measured phase and its warm-up
+            if resident:
+                dl.profile_every = 0
             if env.world_size > 1:
                 t = torch.tensor([dt], dtype=torch.float64)
                 dist.all_reduce(t, op=dist.ReduceOp.MAX, group=env.control_group)
@@ -176,7 +188,14 @@ def main(argv=None):
             bpw = None if zc else dl.batches_per_window[0]
             dl.close()
             if env.rank == 0:
-                if zc:
+                if resident:
+                    per_path = {"path": "resident", "handoff": st["handoff"], "host_waits": st["host_waits"],
+                                "host_us_per_step": round(timing["host_us_per_step"], 1),
+                                "kernel_us": None if timing["kernel_us"] is None else round(timing["kernel_us"], 1),
+                                "kernel_samples": timing["kernel_samples"],
+                                "load_s": round(st["load_s"], 3), "load_gbps": round(st["load_gbps"], 2),
+                                "replica_shared": st["replica_shared"]}
+                elif zc:
                     per_path = {"path": "zerocopy", "max_blocks": st["max_blocks"], "host_waits": st["host_waits"],
                                 "prefault_s": round(st["prefault_s"], 3)}
                 else:

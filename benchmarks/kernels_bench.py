@@ -197,6 +197,7 @@ def main():
     report("column_stats 1Mx9", t, x.numel() * 4)
     del win_bf16, win_u8, win_hwc, raw, pw, x
     out_of_cache(dev)
+    tokens_indexed(dev)
 
 
 def rotating(fns, reps=48):
@@ -239,5 +240,108 @@ def out_of_cache(dev) -> None:
     report("OOC cast f32->bf16 1024 rows (rotating)", rotating(fns), B * img * 6, rows=B)
 
 
+COPY_CEILING_BPS = 5.69e12  # one-pass HBM copy ceiling (docs/PERFORMANCE.md), read + write bytes
+
+
+def tokens_indexed(dev, repeats=5) -> None:
+    """The fused indexed pad/pack kernel against gather_ragged (HBM source) + pad_pack_tokens on the same input:
+    a uint16 corpus far beyond the 256 MB MALL (131072 sequences, lengths uniform in [256, 4096]: ~570 MB), 2048
+    sequences per batch, seq_len 4096, pack. 4 batches (own indices, own outputs: ~300 MB written per rotation)
+    are issued round-robin at launcher level, descriptors already on the device, so the times are device times.
+    One JSON line per repeat and a summary; the outputs of the two routes are compared first."""
+    from ddl_amd import _native
+    from ddl_amd.ops.kernels import carve_token_outputs, segment_sources, token_output_bytes
+
+    hip = _native.hip()
+    rng = np.random.default_rng(0)
+    n_src, B, S, rot = 131072, 2048, 4096, 4
+    lens = rng.integers(256, 4097, size=n_src)
+    offs = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    corpus = torch.randint(0, 32768, (int(offs[-1]),), dtype=torch.int16, device=dev)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    cases = []
+    for _ in range(rot):
+        idx = rng.choice(n_src, size=B, replace=False).astype(np.int64)
+        start = np.ascontiguousarray(offs[idx])
+        dofs = np.concatenate([[0], np.cumsum(offs[idx + 1] - offs[idx])]).astype(np.int64)
+        rs, re_, so = ops.pack_plan(dofs, S)
+        R, n_seg, T = len(rs), len(so) - 1, int(dofs[-1])
+        seg_src = np.ascontiguousarray(segment_sources(start, dofs, so, n_seg))
+        tiles = np.zeros(B + 1, dtype=np.int32)
+        n_tiles = hip.ragged_tile_plan(corpus.data_ptr(), start.ctypes.data, dofs.ctypes.data, B, 2, tiles.ctypes.data)
+        d = {k: torch.from_numpy(v).to(dev) for k, v in dict(start=start, dofs=dofs, rs=rs, re=re_, so=so,
+                                                             seg_src=seg_src, tiles=tiles).items()}
+        flat = torch.empty(T, dtype=torch.int16, device=dev)
+        outs = [carve_token_outputs(torch.empty(token_output_bytes(R, S, n_seg), dtype=torch.uint8, device=dev), R, S,
+                                    n_seg) for _ in range(2)]
+        cases.append((d, flat, outs, R, n_seg, T, n_tiles))
+
+    def out_kw(o):
+        ids, mask, pos, seg, cu = o
+        return dict(out_tokens=ids.data_ptr(), attn_mask=mask.data_ptr(), position_ids=pos.data_ptr(), pos_is_i64=True,
+                    segment_ids=seg.data_ptr(), cu_seqlens_out=cu.data_ptr())
+
+    def fused(c, o=0):
+        d, _, outs, R, n_seg, _, _ = c
+        hip.pad_pack_tokens_indexed(corpus=corpus.data_ptr(), corpus_elems=corpus.numel(),
+                                    src_start=d["start"].data_ptr(), seg_src=d["seg_src"].data_ptr(), offsets=0,
+                                    row_start=d["rs"].data_ptr(), row_end=d["re"].data_ptr(),
+                                    seg_offsets=d["so"].data_ptr(), n_seg=n_seg, rows=R, seq_len=S, pad_id=0, mode=1,
+                                    stream=stream, tok16=True, **out_kw(outs[o]))
+
+    def gather(c):
+        d, flat, _, _, _, _, n_tiles = c
+        hip.gather_ragged(dst=flat.data_ptr(), src=corpus.data_ptr(), src_start=d["start"].data_ptr(),
+                          dst_offsets=d["dofs"].data_ptr(), tile_start=d["tiles"].data_ptr(), n=B, n_tiles=n_tiles,
+                          elem_bytes=2, max_blocks=0, stream=stream)
+
+    def pack(c, o=1):
+        d, flat, outs, R, n_seg, _, _ = c
+        hip.pad_pack_tokens(tokens=flat.data_ptr(), offsets=0, row_start=d["rs"].data_ptr(),
+                            row_end=d["re"].data_ptr(), seg_offsets=d["so"].data_ptr(), n_seg=n_seg, rows=R, seq_len=S,
+                            pad_id=0, mode=1, stream=stream, tok16=True, **out_kw(outs[o]))
+
+    def both(c):
+        gather(c)
+        pack(c)
+
+    for c in cases:  # the two routes write the same bytes
+        fused(c)
+        both(c)
+        torch.cuda.synchronize()
+        assert all(torch.equal(a, b) for a, b in zip(c[2][0], c[2][1])), "fused and two-kernel outputs differ"
+    R_mean = float(np.mean([c[3] for c in cases]))
+    T_mean = float(np.mean([c[5] for c in cases]))
+    wr = 17 * R_mean * S  # ids 4 + i64 positions 8 + segment ids 4 + mask 1 per output position
+    bytes_fused, bytes_two = 2 * T_mean + wr, 2 * T_mean + 2 * T_mean + 2 * T_mean + wr
+    runs = []
+    for r in range(repeats):
+        t = {name: rotating([lambda c=c, fn=fn: fn(c) for c in cases])
+             for name, fn in (("fused", fused), ("gather_ragged", gather), ("pad_pack_tokens", pack),
+                              ("two_kernels", both))}
+        runs.append(t)
+        print(json.dumps({"kernel": "tokens_indexed vs gather_ragged + pad_pack_tokens", "repeat": r,
+                          **{k + "_us": round(v * 1e6, 2) for k, v in t.items()},
+                          "sum_us": round((t["gather_ragged"] + t["pad_pack_tokens"]) * 1e6, 2)}), flush=True)
+    med = {k: float(np.median([t[k] for t in runs])) for k in runs[0]}
+    sums = [t["gather_ragged"] + t["pad_pack_tokens"] for t in runs]
+    print(json.dumps({
+        "kernel": "tokens_indexed summary", "sequences": B, "seq_len": S, "token_dtype": "uint16",
+        "corpus_mb": round(corpus.numel() * 2 / 1e6, 1), "rows": R_mean, "tokens": T_mean, "repeats": repeats,
+        "fused_us_median": round(med["fused"] * 1e6, 2),
+        "fused_us_min_max": [round(min(t["fused"] for t in runs) * 1e6, 2), round(max(t["fused"] for t in runs) * 1e6, 2)],
+        "sum_us_median": round(float(np.median(sums)) * 1e6, 2),
+        "sum_us_min_max": [round(min(sums) * 1e6, 2), round(max(sums) * 1e6, 2)],
+        "two_kernels_back_to_back_us_median": round(med["two_kernels"] * 1e6, 2),
+        "fused_bytes": int(bytes_fused), "two_kernel_bytes": int(bytes_two),
+        "fused_GBps": round(bytes_fused / med["fused"] / 1e9, 1),
+        "two_kernel_GBps": round(bytes_two / float(np.median(sums)) / 1e9, 1),
+        "fused_pct_of_copy_ceiling": round(100 * bytes_fused / med["fused"] / COPY_CEILING_BPS, 1),
+        "fused_tokens_per_s": round(T_mean / med["fused"], 1)}), flush=True)
+
+
 if __name__ == "__main__":
+    if "--only-tokens-indexed" in sys.argv[1:]:  # the one case, e.g. for profiles/resident_tokens/
+        tokens_indexed(torch.device("cuda", 0))
+        sys.exit(0)
     sys.exit(main())

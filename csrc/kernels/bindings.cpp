@@ -24,6 +24,7 @@
 #include "common.h"
 #include "launch.h"
 #include "ragged_index.h"
+#include "tokens_indexed.h"
 #include "engine.h"
 #include "stager.h"
 
@@ -734,6 +735,41 @@ PYBIND11_MODULE(_ddl_hip, m) {
       py::arg("segment_ids"), py::arg("cu_seqlens_out"), py::arg("rows"), py::arg("seq_len"), py::arg("pad_id"),
       py::arg("mode"), py::arg("stream"), py::arg("fill_rows") = 0, py::arg("dev_counts") = 0,
       py::arg("tok16") = false);
+  m.def(
+      "pad_pack_tokens_indexed",
+      [](uintptr_t corpus, int64_t corpus_elems, uintptr_t src_start, uintptr_t seg_src, uintptr_t offsets,
+         uintptr_t row_start, uintptr_t row_end, uintptr_t seg_offsets, int64_t n_seg, uintptr_t out_tokens,
+         uintptr_t attn_mask, uintptr_t position_ids, bool pos_is_i64, uintptr_t segment_ids, uintptr_t cu_seqlens_out,
+         int64_t rows, int64_t seq_len, int pad_id, int mode, uintptr_t stream, int64_t fill_rows, bool tok16) {
+        ddl::TokenSpec sp{};
+        sp.tok16 = tok16 ? 1 : 0;
+        sp.fill_rows = fill_rows;
+        sp.offsets = as_ptr<const int64_t>(offsets);
+        sp.row_start = as_ptr<const int64_t>(row_start);
+        sp.row_end = as_ptr<const int64_t>(row_end);
+        sp.seg_offsets = as_ptr<const int64_t>(seg_offsets);
+        sp.n_seg = n_seg;
+        sp.out_tokens = as_ptr<int32_t>(out_tokens);
+        sp.attn_mask = as_ptr<uint8_t>(attn_mask);
+        sp.position_ids = as_ptr<void>(position_ids);
+        sp.pos_is_i64 = pos_is_i64 ? 1 : 0;
+        sp.segment_ids = as_ptr<int32_t>(segment_ids);
+        sp.cu_seqlens_out = as_ptr<int32_t>(cu_seqlens_out);
+        sp.rows = rows;
+        sp.seq_len = seq_len;
+        sp.pad_id = pad_id;
+        sp.mode = mode;
+        check_rc(ddl::pad_pack_tokens_indexed(sp, as_ptr<const void>(corpus), corpus_elems,
+                                              as_ptr<const int64_t>(src_start), as_ptr<const int64_t>(seg_src),
+                                              as_stream(stream)),
+                 "pad_pack_tokens_indexed");
+      },
+      py::arg("corpus"), py::arg("corpus_elems"), py::arg("src_start"), py::arg("seg_src"), py::arg("offsets"),
+      py::arg("row_start"), py::arg("row_end"), py::arg("seg_offsets"), py::arg("n_seg"), py::arg("out_tokens"),
+      py::arg("attn_mask"), py::arg("position_ids"), py::arg("pos_is_i64"), py::arg("segment_ids"),
+      py::arg("cu_seqlens_out"), py::arg("rows"), py::arg("seq_len"), py::arg("pad_id"), py::arg("mode"),
+      py::arg("stream"), py::arg("fill_rows") = 0, py::arg("tok16") = false);
+  m.attr("TOKEN_SEG_LDS_CAP") = ddl::kTiSegCap;
   m.attr("RAGGED_MAP_CAP") = ddl::kRaggedMapCap;
   m.def(
       "ragged_tile_plan",

@@ -129,6 +129,17 @@ int pack_plan_device(const PackPlanSpec& spec, hipStream_t st);
 constexpr int kMaxTokenSubs = 16;
 int pad_pack_tokens_multi(const TokenSpec* specs, int n, hipStream_t st);
 
+// tokens_indexed.hip --------------------------------------------------------
+// pad_pack_tokens for the virtual flat stream concat(corpus[src_start[i] : src_start[i] + len_i]), every token
+// read from the corpus (HBM) instead: spec.tokens is null, the plan arrays (offsets [B + 1] in pad mode,
+// row_start / row_end / seg_offsets in pack mode) are positions of that virtual stream as for pad_pack_tokens.
+// corpus: int32, or uint16 when spec.tok16, corpus_elems elements; src_start [B] (pad mode) and seg_src
+// [n_seg] (pack mode: the corpus element of each segment's first token) are device-readable. A plan built on
+// the device (dev_counts) is not supported. Outputs of a row width that is a multiple of 4 must be 16-byte
+// aligned (the mask 4-byte). Block 0 writes cu_seqlens_out even when there is no row.
+int pad_pack_tokens_indexed(const TokenSpec& spec, const void* corpus, int64_t corpus_elems, const int64_t* src_start,
+                            const int64_t* seg_src, hipStream_t st);
+
 // ragged.hip ----------------------------------------------------------------
 // Device twin of the host gather_ragged: sequence i (src_start[i] elements into src, dst_offsets[i + 1] -
 // dst_offsets[i] elements of elem_bytes = 2 or 4) -> dst[dst_offsets[i] ...). src: HBM or pinned,

@@ -20,6 +20,7 @@ __all__ = [
     "EpochOrder",
     "IndexedProducer",
     "ZeroCopyTokenLoader",
+    "ResidentTokenLoader",
     "DataLoader",
     "OutputSpec",
     "StagingSpec",
@@ -46,6 +47,10 @@ def __getattr__(name):
         from .zerocopy_tokens import ZeroCopyTokenLoader
 
         return ZeroCopyTokenLoader
+    if name == "ResidentTokenLoader":
+        from .resident_tokens import ResidentTokenLoader
+
+        return ResidentTokenLoader
     if name == "DataLoader":
         from .frontend import DataLoader
 

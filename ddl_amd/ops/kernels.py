@@ -799,6 +799,163 @@ def pack_tokens(tokens: torch.Tensor, seq_offsets, seq_len: int, pad_id: int = 0
     return out, mask, pos, seg, so_d.to(torch.int32)
 
 
+# ------------------------------------------------- tokens out of an HBM corpus
+def _align16(n: int) -> int:
+    return -(-int(n) // 16) * 16
+
+
+def token_output_bytes(rows: int, seq_len: int, n_seg: int | None = None, position_dtype=torch.int64) -> int:
+    """Bytes of the one allocation that ``carve_token_outputs`` cuts a [rows, seq_len] token batch from
+    (``n_seg`` None: pad mode, no segment ids and no cu_seqlens)."""
+    n = int(rows) * int(seq_len)
+    pb = 8 if position_dtype == torch.int64 else 4
+    total = _align16(pb * n) + _align16(4 * n) + _align16(n)
+    if n_seg is not None:
+        total += _align16(4 * (int(n_seg) + 1)) + _align16(4 * n)
+    return total
+
+
+def carve_token_outputs(whole: torch.Tensor, rows: int, seq_len: int, n_seg: int | None = None,
+                        position_dtype=torch.int64):
+    """(input_ids, attention_mask, position_ids, segment_ids | None, cu_seqlens | None) as views of the uint8
+    buffer ``whole``, in the order ``collate_token_window`` lays them out (position ids, cu_seqlens, input ids,
+    segment ids, mask), every region starting 16-byte aligned."""
+    R, S = int(rows), int(seq_len)
+    n = R * S
+    pb = 8 if position_dtype == torch.int64 else 4
+    o = 0
+    pos = whole[o:o + pb * n].view(position_dtype).view(R, S)
+    o += _align16(pb * n)
+    cu = seg = None
+    if n_seg is not None:
+        cu = whole[o:o + 4 * (n_seg + 1)].view(torch.int32)
+        o += _align16(4 * (n_seg + 1))
+    ids = whole[o:o + 4 * n].view(torch.int32).view(R, S)
+    o += _align16(4 * n)
+    if n_seg is not None:
+        seg = whole[o:o + 4 * n].view(torch.int32).view(R, S)
+        o += _align16(4 * n)
+    mask = whole[o:o + n].view(R, S)
+    return ids, mask, pos, seg, cu
+
+
+def _token_out_buffer(out, need: int, dev) -> torch.Tensor:
+    if out is None:
+        return torch.empty(need, dtype=torch.uint8, device=dev)
+    if (not out.is_cuda or out.dtype != torch.uint8 or out.dim() != 1 or not out.is_contiguous()
+            or out.numel() < need or out.data_ptr() % 16):
+        raise ValueError(f"out must be a contiguous 16-byte aligned uint8 device buffer of >= {need} bytes")
+    return out[:need]
+
+
+def segment_sources(src_start: np.ndarray, offsets: np.ndarray, seg_offsets: np.ndarray, n_seg: int) -> np.ndarray:
+    """``seg_src`` [n_seg]: the corpus element of each segment's first token, for sequences that start at corpus
+    elements ``src_start`` [n] and at ``offsets`` [n + 1] of the virtual flat stream the plan's ``seg_offsets``
+    refer to. A segment is a piece of one sequence: the last one that starts at or before it (an empty sequence
+    shares its start with the next one and holds no segment)."""
+    so = seg_offsets[:n_seg]
+    q = np.searchsorted(offsets, so, side="right") - 1
+    return src_start[q] + (so - offsets[q])
+
+
+def _indexed_args(corpus, corpus_offsets, idx, position_dtype):
+    if position_dtype not in (torch.int64, torch.int32):
+        raise TypeError("position_dtype must be int64 or int32")
+    if not isinstance(corpus, torch.Tensor) or (corpus.dtype != torch.int32 and corpus.dtype not in _TOK16):
+        raise TypeError("corpus must be a flat int32 / 16-bit token tensor")
+    if not corpus.is_contiguous():
+        raise ValueError("corpus must be contiguous")
+    flat, start, dofs = _ragged_args(corpus, corpus_offsets, idx)
+    if int(dofs[-1]) > 0x7FFFFFFF:
+        raise ValueError(f"{int(dofs[-1])} tokens in one batch overflow int32 cu_seqlens")
+    return flat, np.ascontiguousarray(start, dtype=np.int64), dofs
+
+
+def _upload_words(words: np.ndarray, dev, stream):
+    handle = _stream_handle(stream)
+    if isinstance(stream, int):
+        stream = torch.cuda.ExternalStream(stream, device=dev)
+    with torch.cuda.stream(stream):  # None: the current stream. The descriptor is allocated and copied on it
+        desc = torch.from_numpy(words).to(dev)  # a pageable copy: complete for the host on return
+    return desc, handle, stream
+
+
+def pad_tokens_indexed(corpus: torch.Tensor, corpus_offsets, idx, seq_len: int, pad_id: int = 0,
+                       position_dtype=torch.int64, out: torch.Tensor | None = None, stream=None):
+    """``pad_tokens`` of sequences ``idx`` of a corpus that lives in HBM, in one pass: ``corpus`` is the flat
+    device tensor (int32 or 16-bit ids), sequence i = ``corpus[corpus_offsets[i]:corpus_offsets[i + 1]]``;
+    ``corpus_offsets`` and ``idx`` live on the host. The gathered stream is never materialised (the
+    ``pad_pack_tokens_indexed`` kernel reads every token from the corpus). Returns (tokens [B,S] i32, mask u8
+    [B,S], position ids [B,S]); ``out``: a uint8 device buffer the three are carved from
+    (``token_output_bytes`` / ``carve_token_outputs``). A CPU corpus takes the reference path
+    (``ref_gather_ragged`` + ``ref_pad_tokens``)."""
+    flat, start, dofs = _indexed_args(corpus, corpus_offsets, idx, position_dtype)
+    S = int(seq_len)
+    if S <= 0:
+        raise ValueError("seq_len must be > 0")
+    if not flat.is_cuda:
+        tokens, offs = ref_gather_ragged(flat, corpus_offsets, idx)
+        return ref_pad_tokens(tokens, offs, S, pad_id, position_dtype)
+    n, dev = int(start.size), flat.device
+    words = np.concatenate([start, dofs])  # one descriptor: src_start [n], offsets [n + 1]
+    desc, handle, stream = _upload_words(words, dev, stream)
+    with torch.cuda.stream(stream):
+        whole = _token_out_buffer(out, token_output_bytes(n, S, None, position_dtype), dev)
+    ids, mask, pos, _, _ = carve_token_outputs(whole, n, S, None, position_dtype)
+    base = desc.data_ptr()
+    _native.hip().pad_pack_tokens_indexed(
+        corpus=flat.data_ptr(), corpus_elems=flat.numel(), src_start=base, seg_src=0, offsets=base + 8 * n,
+        row_start=0, row_end=0, seg_offsets=0, n_seg=0, out_tokens=ids.data_ptr(), attn_mask=mask.data_ptr(),
+        position_ids=pos.data_ptr(), pos_is_i64=position_dtype == torch.int64, segment_ids=0, cu_seqlens_out=0,
+        rows=n, seq_len=S, pad_id=pad_id, mode=0, stream=handle, tok16=flat.dtype in _TOK16)
+    return ids, mask, pos
+
+
+def pack_tokens_indexed(corpus: torch.Tensor, corpus_offsets, idx, seq_len: int, pad_id: int = 0,
+                        position_dtype=torch.int64, fill_rows: int = 0, out: torch.Tensor | None = None, stream=None):
+    """``pack_tokens`` of sequences ``idx`` of a corpus that lives in HBM, in one pass (see
+    ``pad_tokens_indexed``): the host computes the sequences' running offsets, the native ``pack_plan`` and each
+    segment's corpus element, uploads them as one descriptor, and the ``pad_pack_tokens_indexed`` kernel packs
+    straight out of the corpus. Returns (tokens [R,S] i32, mask [R,S] u8, position_ids [R,S], segment_ids [R,S]
+    i32 (-1 = pad), cu_seqlens [n_seg+1] i32); ``fill_rows`` > packed rows: padding rows up to that count;
+    ``out``: a uint8 device buffer the five are carved from. A CPU corpus takes the reference path
+    (``ref_gather_ragged`` + ``ref_pack_plan`` + ``ref_pack_tokens``)."""
+    flat, start, dofs = _indexed_args(corpus, corpus_offsets, idx, position_dtype)
+    S = int(seq_len)
+    if S <= 0:
+        raise ValueError("seq_len must be > 0")
+    if not flat.is_cuda:
+        tokens, offs = ref_gather_ragged(flat, corpus_offsets, idx)
+        rs, re_, so = ref_pack_plan(offs.numpy(), S)
+        return (*ref_pack_tokens(tokens, rs, re_, so, S, pad_id, position_dtype, fill_rows=fill_rows),
+                torch.from_numpy(so.astype(np.int32)))
+    n, dev = int(start.size), flat.device
+    lens = np.diff(dofs)
+    cap = max(int(np.sum(-(-lens // S))) if n else 0, 1)  # segments (>= rows) of this batch
+    # one descriptor: src_start [n], offsets [n + 1], row_start [cap], row_end [cap], seg_offsets [cap + 1],
+    # seg_src [cap]
+    words = np.zeros(2 * n + 1 + 4 * cap + 1, dtype=np.int64)
+    words[:n], words[n:2 * n + 1] = start, dofs
+    o_rs, o_re, o_so, o_ss = 2 * n + 1, 2 * n + 1 + cap, 2 * n + 1 + 2 * cap, 2 * n + 2 + 3 * cap
+    n_rows, n_seg = _native.runtime().pack_plan(words[n:].ctypes.data, n, S, words[o_rs:].ctypes.data,
+                                                words[o_re:].ctypes.data, cap, words[o_so:].ctypes.data, cap)
+    words[o_ss:o_ss + n_seg] = segment_sources(start, dofs, words[o_so:], n_seg)
+    R = max(int(n_rows), int(fill_rows))
+    desc, handle, stream = _upload_words(words, dev, stream)
+    with torch.cuda.stream(stream):
+        whole = _token_out_buffer(out, token_output_bytes(R, S, n_seg, position_dtype), dev)
+    ids, mask, pos, seg, cu = carve_token_outputs(whole, R, S, n_seg, position_dtype)
+    base = desc.data_ptr()
+    _native.hip().pad_pack_tokens_indexed(
+        corpus=flat.data_ptr(), corpus_elems=flat.numel(), src_start=base, seg_src=base + 8 * o_ss, offsets=0,
+        row_start=base + 8 * o_rs, row_end=base + 8 * o_re, seg_offsets=base + 8 * o_so, n_seg=n_seg,
+        out_tokens=ids.data_ptr(), attn_mask=mask.data_ptr(), position_ids=pos.data_ptr(),
+        pos_is_i64=position_dtype == torch.int64, segment_ids=seg.data_ptr(), cu_seqlens_out=cu.data_ptr(),
+        rows=n_rows, seq_len=S, pad_id=pad_id, mode=1, stream=handle, fill_rows=int(fill_rows),
+        tok16=flat.dtype in _TOK16)
+    return ids, mask, pos, seg, cu
+
+
 # ----------------------------------------------------------------- reductions
 def ref_checksum(x: torch.Tensor) -> int:
     b = x.detach().contiguous().reshape(-1).view(torch.uint8).cpu().numpy()

@@ -1,0 +1,301 @@
+"""HBM-resident token loader (BASELINE config 4): the corpus is copied into HBM once, and every batch is packed
+straight out of it by one kernel.
+
+``TokenBatchProducer`` and ``ZeroCopyTokenLoader`` put the PCIe link and host DRAM under every token of every
+epoch. A tokenised corpus is the dataset most likely to fit in HBM (2 bytes per id: 10B tokens are 20 GB of
+288), and once it is there a step needs no link, no host DRAM pass and no producers, so a rank's rate no longer
+depends on how many ranks share a socket. Here
+
+* bring-up copies the corpus tokens (node shm) into one HBM allocation in ``chunk_bytes`` pieces: the mapping is
+  registered (shared with any zero-copy loader over it), copied with SDMA and unregistered again. The offsets
+  stay on the host, where the plan is built. At W > 1 every rank loads its own full replica, with no
+  collective; a corpus larger than ``hbm_fraction`` of the free HBM is refused (sharding is not supported: use
+  ``ZeroCopyTokenLoader``). Loaders over one corpus on one device (train + eval) share one replica, counted per
+  process and freed when the last one closes;
+* per step the host does what ``ZeroCopyTokenLoader`` does minus the tile plan: this rank's ``EpochOrder``
+  indices, the lengths, the producer's FFD rule, the native ``pack_plan`` -- written as a
+  ``TokenWindowLayout(k=1)`` header plus ``src_start`` / ``seg_src`` into a slot of a small pinned ring;
+* the prep stream copies that slot to the device (one small H2D) and launches ``pad_pack_tokens_indexed`` once:
+  it writes the model inputs of the virtual stream ``concat(corpus[src_start[i] : src_start[i] + len_i])``
+  reading every token from the corpus -- no flat window is written and read back.
+
+The batches are those of the other two token paths, key by key, and the order and the ``kind="indexed"``
+checkpoint are ``PrefetchedIndexedLoader``'s: a run resumes from a ``TokenBatchProducer`` or
+``ZeroCopyTokenLoader`` checkpoint and back, at any world size. With ``device="cpu"`` the same planning runs
+with the host ``gather_ragged`` and the host collate.
+"""
+
+from __future__ import annotations
+
+import time
+
+import numpy as np
+import torch
+
+from . import _native
+from .exceptions import DDLError
+from .models.tokens import (META_FIELDS, SharedTokenSource, TokenWindowLayout, collate_token_window,
+                            drop_cached_views, ffd_order, in_order_rows)
+from .ops.kernels import carve_token_outputs, segment_sources, token_output_bytes
+from .permutation import EpochOrder
+from .resident import PrefetchedIndexedLoader
+from .types import DDLEnv
+from .utils import streams
+from .zerocopy import register_mapping, unregister_mapping
+
+_REPLICAS: dict[tuple, list] = {}  # (corpus address, bytes, device index) -> [HBM tensor, users, load seconds]
+
+
+def _acquire_replica(source: SharedTokenSource, nbytes: int, device: torch.device, stream, hbm_fraction: float,
+                     chunk_bytes: int) -> tuple[tuple, torch.Tensor, bool]:
+    """(key, the corpus in HBM, shared with an earlier loader). A new replica is budgeted against the free HBM
+    first; a failure leaves nothing allocated or registered."""
+    key = (int(source.tokens.address), int(nbytes), device.index)
+    rep = _REPLICAS.get(key)
+    if rep is not None:
+        rep[1] += 1
+        return key, rep[0], True
+    free, _ = torch.cuda.mem_get_info(device)
+    if nbytes > hbm_fraction * free:
+        raise DDLError(f"the corpus ({nbytes} bytes) exceeds hbm_fraction={hbm_fraction} of the free HBM "
+                       f"({free} bytes free, {int(hbm_fraction * free)} allowed); a corpus is not sharded across "
+                       "ranks: use ZeroCopyTokenLoader, which reads it from host memory")
+    t0 = time.perf_counter()
+    hip = _native.hip()
+    hbm = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
+    if nbytes:
+        torch.cuda.synchronize(device)  # the block may be a cached one: nothing of its past is still running
+        base, _ = register_mapping(source.tokens.address, nbytes, shared=True)  # pinned: the copies are SDMA
+        try:
+            step = max(1, int(chunk_bytes))
+            for o in range(0, nbytes, step):
+                hip.memcpy_h2d(hbm.data_ptr() + o, source.tokens.address + o, min(step, nbytes - o),
+                               stream.cuda_stream)
+            stream.synchronize()
+        finally:
+            unregister_mapping(base, device, shared=True)
+    _REPLICAS[key] = [hbm, 1, time.perf_counter() - t0]
+    return key, hbm, False
+
+
+def _release_replica(key: tuple) -> None:
+    rep = _REPLICAS.get(key)
+    if rep is None:
+        return
+    rep[1] -= 1
+    if rep[1] <= 0:
+        del _REPLICAS[key]  # the last reference: the allocation goes back to the allocator
+
+
+class ResidentTokenLoader(PrefetchedIndexedLoader):
+    def __init__(self, source: SharedTokenSource, global_batch: int, seq_len: int = 4096, mode: str = "pad",
+                 env: DDLEnv | None = None, *, seed: int = 0, pack_order: str = "in_order",
+                 token_rows: str = "exact", pad_id: int = 0, depth: int = 2,
+                 device: str | torch.device | None = None, n_epochs: int | None = None,
+                 resume_state: dict | None = None, handoff: str = "device", hbm_fraction: float = 0.8,
+                 chunk_bytes: int = 256 << 20):
+        if handoff not in ("host", "device"):
+            raise ValueError("handoff must be 'host' or 'device'")
+        if mode not in ("pad", "pack"):
+            raise ValueError("mode must be 'pad' or 'pack'")
+        if pack_order not in ("in_order", "ffd"):
+            raise ValueError("pack_order must be 'in_order' or 'ffd'")
+        if pack_order != "in_order" and mode != "pack":
+            raise ValueError(f"pack_order={pack_order!r} reorders rows of a PACKED batch; mode={mode!r} has "
+                             "one sequence per row")
+        if token_rows not in ("exact", "fixed"):
+            raise ValueError("token_rows must be 'exact' or 'fixed'")
+        self.handoff = handoff  # batches take microseconds, not a PCIe transfer: the caller's stream waits
+        self.env = env or DDLEnv()
+        self.W, self.rank = self.env.world_size, self.env.rank
+        self.source, self.seq_len, self.mode = source, int(seq_len), mode
+        self.pack_order, self.token_rows, self.pad_id = pack_order, token_rows, int(pad_id)
+        self.order = EpochOrder(source.n, global_batch, seed)
+        self.GB, self.LB = int(global_batch), self.order.local_batch(self.W)
+        self.out_dtype = torch.int32  # input_ids (the checkpoint's dtype field)
+        if device is None:
+            device = self.env.device or ("cuda" if torch.cuda.is_available() else "cpu")
+        self.device = torch.device(device)
+        if self.device.type == "cuda" and self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self._init_cursor(seed, depth, n_epochs, resume_state)
+
+        lay = self.layout = TokenWindowLayout(self.LB, self.seq_len, source.max_len, 1, source.token_bytes)
+        self._reg = lay.regions()
+        self._hdr_bytes = self._reg["tokens"][0]  # meta + header arrays: everything in front of the tokens
+        # in front of the header: the kernel's descriptor, src_start [LB] i64 + seg_src [max_segments] i64
+        self._desc_bytes = -(-8 * (self.LB + lay.max_segments) // 16) * 16
+        self._toks = source.tokens.tensor().view(-1)  # keeps the mappings alive
+        self._offs_t = source.offsets.tensor().view(-1)
+        self._offs = self._offs_t.numpy()
+        self.n_elems = int(self._offs[-1]) if source.n else 0
+        self.nbytes = self.n_elems * source.token_bytes
+        self.prep_stream = None
+        self._replica_key = None
+        self.replica_shared = False
+        self.load_s = 0.0
+        self.assemble_s = 0.0  # wall time spent in _assemble (host_us_per_step of the benchmark)
+        self.profile_every = 0  # > 0: device events around the launch of every profile_every-th step
+        self._kernel_evs: list = []
+        self._windows: list = []
+        gpu = self.device.type == "cuda"
+        if gpu:
+            self.prep_stream = streams.batch_stream(self.device)
+            self._replica_key, self._hbm, self.replica_shared = _acquire_replica(
+                source, self.nbytes, self.device, self.prep_stream, float(hbm_fraction), chunk_bytes)
+            self.load_s = _REPLICAS[self._replica_key][2]
+            win_bytes = self._desc_bytes + self._hdr_bytes  # descriptor + header only: no token ever lands here
+            self._windows = [torch.empty(win_bytes, dtype=torch.uint8, device=self.device)
+                             for _ in range(self.depth + 1)]
+            # pinned slots, one more than the windows: a slot is rewritten only after the copy out of it has
+            # completed (its event), which is normally long done
+            self._slots = [torch.empty(win_bytes, dtype=torch.uint8, pin_memory=True) for _ in range(self.depth + 2)]
+            self._slot_ev = [None] * len(self._slots)
+        else:
+            self._windows = [torch.empty(self._desc_bytes + lay.nbytes, dtype=torch.uint8)
+                             for _ in range(self.depth + 1)]
+            self._slots = self._windows  # the CPU twin writes the header straight into the window
+        self._views = [self._host_views(b) for b in self._slots]
+
+    @property
+    def replica_ptr(self) -> int | None:
+        """Device address of the corpus replica (None on the CPU, and after ``close``)."""
+        return self._hbm.data_ptr() if self._replica_key is not None else None
+
+    def _host_views(self, buf: torch.Tensor) -> dict:
+        """numpy views (and raw addresses) of the descriptor and header arrays at the front of a host buffer."""
+        a = buf.numpy()
+        d, LB = self._desc_bytes, self.LB
+        v = {"src_start": a[:8 * LB].view(np.int64),
+             "seg_src": a[8 * LB:8 * (LB + self.layout.max_segments)].view(np.int64)}
+        for name in ("meta", "offsets", "row_start", "row_end", "seg_offsets"):
+            off, count = self._reg[name]
+            v[name] = a[d + off:d + off + 8 * count].view(np.int64)
+        v["ptr"] = {k: int(x.ctypes.data) for k, x in v.items()}
+        return v
+
+    def _assemble(self, t: int):
+        t_host = time.perf_counter()
+        e, g = divmod(t, self.order.batches_per_epoch)
+        lay, S, LB, tb = self.layout, self.seq_len, self.LB, self.source.token_bytes
+        offs = self._offs
+        idx = np.asarray(self.order.indices(e, g, self.rank, self.W), dtype=np.int64)
+        lens = offs[idx + 1] - offs[idx]
+        pack = self.mode == "pack"
+        if pack and self.pack_order == "ffd":
+            order, ffd_rows = ffd_order(lens, S)
+            if ffd_rows < in_order_rows(lens, S):  # the producer's rule: FFD is kept only if it wins
+                idx, lens = idx[order], lens[order]
+        gpu = self.prep_stream is not None
+        k = t % len(self._slots)
+        if gpu and self._slot_ev[k] is not None and not self._slot_ev[k].query():
+            self._slot_ev[k].synchronize()  # the H2D copy out of this slot (depth + 2 batches ago)
+        v = self._views[k]
+        p = v["ptr"]
+        v["src_start"][:] = offs[idx]
+        v["offsets"][0] = 0
+        np.cumsum(lens, out=v["offsets"][1:])
+        n_tokens = int(v["offsets"][LB])
+        if n_tokens > self._reg["tokens"][1]:
+            raise ValueError(f"{n_tokens} tokens exceed the layout's {self._reg['tokens'][1]}: the corpus holds a "
+                             "sequence longer than source.max_len")
+        n_rows = n_seg = max_seg = 0
+        if pack:
+            cap = lay.max_segments
+            n_rows, n_seg = _native.runtime().pack_plan(p["offsets"], LB, S, p["row_start"], p["row_end"], cap,
+                                                        p["seg_offsets"], cap)
+            if n_seg:
+                max_seg = int(np.diff(v["seg_offsets"][: n_seg + 1]).max())
+        meta = (n_tokens, n_rows, n_seg, max_seg, 0)
+        v["meta"][:META_FIELDS] = meta
+        win = self._windows[t % len(self._windows)]
+        fixed = self.token_rows == "fixed"
+        if not gpu:
+            _native.runtime().gather_ragged(win.data_ptr() + self._desc_bytes + self._hdr_bytes, p["offsets"],
+                                            self._toks.data_ptr(), self._offs_t.data_ptr(), self.source.n, idx, tb,
+                                            self._reg["tokens"][1], 2)
+            batch = collate_token_window(win[self._desc_bytes:], lay, self.mode, meta, self.pad_id, fixed_rows=fixed)
+            self.assemble_s += time.perf_counter() - t_host
+            return batch, None
+        if n_tokens > 0x7FFFFFFF:
+            raise ValueError(f"{n_tokens} tokens in one batch overflow int32 cu_seqlens")
+        if pack and n_seg:
+            v["seg_src"][:n_seg] = segment_sources(v["src_start"], v["offsets"], v["seg_offsets"], n_seg)
+        hip, st = _native.hip(), self.prep_stream
+        fill = lay.max_segments if (pack and fixed) else 0
+        R = max(n_rows, fill) if pack else LB
+        timed = self.profile_every > 0 and t % self.profile_every == 0
+        with streams.on_stream(st):
+            w = win.data_ptr()
+            hip.memcpy_h2d(w, self._slots[k].data_ptr(), self._desc_bytes + self._hdr_bytes, st.cuda_stream)
+            if self._slot_ev[k] is None:
+                self._slot_ev[k] = torch.cuda.Event()
+            self._slot_ev[k].record(st)
+            # one allocation for all outputs, laid out as collate_token_window's: memory of its own, so a held
+            # batch survives the rings
+            whole = torch.empty(token_output_bytes(R, S, n_seg if pack else None), dtype=torch.uint8,
+                                device=self.device)
+            ids, mask, pos, seg, cu = carve_token_outputs(whole, R, S, n_seg if pack else None)
+            h = w + self._desc_bytes
+            if timed:
+                ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                ev0.record(st)
+            hip.pad_pack_tokens_indexed(
+                corpus=self._hbm.data_ptr(), corpus_elems=self.n_elems, src_start=w, seg_src=w + 8 * LB,
+                offsets=h + self._reg["offsets"][0], row_start=h + self._reg["row_start"][0],
+                row_end=h + self._reg["row_end"][0], seg_offsets=h + self._reg["seg_offsets"][0], n_seg=n_seg,
+                out_tokens=ids.data_ptr(), attn_mask=mask.data_ptr(), position_ids=pos.data_ptr(), pos_is_i64=True,
+                segment_ids=seg.data_ptr() if pack else 0, cu_seqlens_out=cu.data_ptr() if pack else 0,
+                rows=n_rows if pack else LB, seq_len=S, pad_id=self.pad_id, mode=1 if pack else 0,
+                stream=st.cuda_stream, fill_rows=fill, tok16=tb == 2)
+            if timed:
+                ev1.record(st)
+                self._kernel_evs.append((ev0, ev1))
+            ev = torch.cuda.Event()
+            ev.record(st)
+        if pack:
+            batch = {"input_ids": ids, "attention_mask": mask, "position_ids": pos, "segment_ids": seg,
+                     "cu_seqlens": cu, "max_seqlen": max_seg, "n_tokens": n_tokens}
+            if fixed:
+                batch["n_rows"] = n_rows
+        else:
+            batch = {"input_ids": ids, "attention_mask": mask, "position_ids": pos, "n_tokens": n_tokens}
+        self.assemble_s += time.perf_counter() - t_host
+        return batch, ev
+
+    def timing(self) -> dict:
+        """``host_us_per_step``: mean wall time of ``_assemble`` (planning, the H2D and the launch, on the host);
+        ``kernel_us``: mean device time of the sampled launches (``profile_every``), None without samples.
+        Synchronises the prep stream."""
+        steps = max(1, self.batches + len(self._queue))  # batches assembled so far
+        out = {"host_us_per_step": 1e6 * self.assemble_s / steps, "kernel_us": None,
+               "kernel_samples": len(self._kernel_evs)}
+        if self._kernel_evs:
+            self.prep_stream.synchronize()
+            out["kernel_us"] = 1e3 * sum(a.elapsed_time(b) for a, b in self._kernel_evs) / len(self._kernel_evs)
+        return out
+
+    def stats(self) -> dict:
+        return {"batches": self.batches, "source_bytes": self.nbytes, "load_s": self.load_s,
+                "load_gbps": self.nbytes / self.load_s / 1e9 if self.load_s > 0 else 0.0,
+                "handoff": self.handoff, "host_waits": self.host_waits, "replica_shared": self.replica_shared}
+
+    def close(self) -> None:
+        if self.prep_stream is not None:
+            self.prep_stream.synchronize()
+        self._queue.clear()
+        self._kernel_evs = []
+        if self._windows:
+            if self.prep_stream is None:
+                drop_cached_views(w.data_ptr() + self._desc_bytes for w in self._windows)
+            self._windows = []
+        if self._replica_key is not None:
+            key, self._replica_key = self._replica_key, None
+            self._hbm = None
+            _release_replica(key)
+
+    def __del__(self):  # pragma: no cover - best effort
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -24,6 +24,10 @@ batch on the GPU with the pad/pack kernel:
 gathers each batch's ragged sequences straight out of it over PCIe (no host copy; every token is read from
 DRAM once). Same batches, same checkpoint.
 
+``--resident`` needs no producers and no link either: ``ResidentTokenLoader`` copies the corpus into HBM once (it
+must fit: 2-4 bytes per token) and one gfx950 kernel packs every batch straight out of it. Same batches, same
+checkpoint. ``DDL_DEVICE=cpu`` runs it (and ``--zero-copy``) with the host twin.
+
 ``state_dict()`` is the indexed-kind cursor (seed, epoch, global batch), so a
 job can resume at another world size.
 """
@@ -47,13 +51,17 @@ def main() -> None:
     ap.add_argument("--batches-per-window", type=int, default=4)
     ap.add_argument("--zero-copy", action="store_true",
                     help="no producers: the GPU gathers the batches out of the registered corpus")
+    ap.add_argument("--resident", action="store_true",
+                    help="no producers, no PCIe per step: the corpus lives in HBM and one kernel packs the batches")
     a = ap.parse_args()
+    if a.zero_copy and a.resident:
+        ap.error("--zero-copy and --resident are two loaders: pick one")
 
     name = f"ddl_amd_example_tok_{os.environ.get('MASTER_PORT', os.getpid())}"
     creator = int(os.environ.get("LOCAL_RANK", "0")) == 0
     src = SharedTokenSource.synthetic(name, a.n_seqs, 64, a.seq_len, seed=0) if creator else None
     try:
-        with ddl_amd.start(n_producers=0 if a.zero_copy else 2) as (env, conn):
+        with ddl_amd.start(n_producers=0 if (a.zero_copy or a.resident) else 2) as (env, conn):
             if env.world_size > 1:
                 torch.distributed.barrier(group=env.control_group)
             if src is None:  # other local ranks attach to the creator's segments
@@ -63,7 +71,10 @@ def main() -> None:
                 n_tok = int(offs.tensor()[-1])
                 src = SharedTokenSource(SharedArraySource(name + "_tok", n_tok, (1,), "int32"), offs, a.seq_len)
             pack_order = "ffd" if a.mode == "pack" else "in_order"
-            if a.zero_copy:
+            if a.resident:
+                dl = ddl_amd.ResidentTokenLoader(src, a.global_batch, a.seq_len, a.mode, env, pack_order=pack_order,
+                                                 n_epochs=a.epochs)
+            elif a.zero_copy:
                 dl = ddl_amd.ZeroCopyTokenLoader(src, a.global_batch, a.seq_len, a.mode, env, pack_order=pack_order,
                                                  n_epochs=a.epochs)
             else:
@@ -85,7 +96,11 @@ def main() -> None:
                     print(f"epoch {epoch}: {rows} rows x {a.seq_len} on rank 0, {real} real tokens "
                           f"({100.0 * real / max(rows * a.seq_len, 1):.1f}% dense){extra}; keys {sorted(b)}",
                           flush=True)
-            if a.zero_copy:
+            if a.resident and env.rank == 0:
+                st = dl.stats()
+                where = f"in HBM, loaded in {st['load_s']:.3f} s" if st["load_s"] else "read in place (CPU twin)"
+                print(f"resident corpus: {st['source_bytes']} bytes {where}, hand-off {st['handoff']}", flush=True)
+            if a.zero_copy or a.resident:
                 dl.close()
     finally:
         if src is not None:
