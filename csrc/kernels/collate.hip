@@ -19,6 +19,8 @@ namespace {
 
 constexpr int kThreads = 256;
 constexpr int kPix = 2048;  // pixels per tile: 8 per lane
+// Dynamic LDS a launch may ask for without raising the kernel's limit through a function attribute.
+constexpr size_t kPlainLdsBytes = 64 * 1024;
 
 template <typename T>
 struct Px;
@@ -59,17 +61,18 @@ struct Out8 {
   }
 };
 
-// grid: (tiles_per_image * batch); LDS: kPix * C * sizeof(Tin) bytes.
+// grid: (tiles_per_image * batch); LDS: tile_px * C * sizeof(Tin) bytes. tile_px is kPix, or a smaller
+// multiple of 8 for wide pixels (launch_hwc); lanes past the tile's pixels only help to stage it.
 template <typename Tin, int OUT_BF16>
 __global__ void __launch_bounds__(kThreads) hwc_to_chw_kernel(void* __restrict__ dst, const Tin* __restrict__ src,
                                                               int64_t pixels, int32_t channels, int64_t tiles,
-                                                              RowIndex ri, Affine aff) {
+                                                              int32_t tile_px, RowIndex ri, Affine aff) {
   extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
   Tin* tile = reinterpret_cast<Tin*>(lds_raw);
   const int64_t img = blockIdx.x / static_cast<uint32_t>(tiles);  // 32-bit: grid < 2^32 blocks
   const int64_t t = blockIdx.x - static_cast<uint32_t>(img) * static_cast<uint32_t>(tiles);
-  const int64_t p0 = t * kPix;
-  const int npx = static_cast<int>(pixels - p0 < kPix ? pixels - p0 : kPix);
+  const int64_t p0 = t * tile_px;
+  const int npx = static_cast<int>(pixels - p0 < tile_px ? pixels - p0 : tile_px);
   const int64_t srow = source_row(ri, img);
   const Tin* s = src + (srow * pixels + p0) * channels;
   const int elems = npx * channels;
@@ -175,12 +178,19 @@ __global__ void __launch_bounds__(kThreads) hwc3_u8_to_chw_kernel(void* __restri
   }
 }
 
+// LDS bytes one workgroup of the generic kernel may request on the current device: the device's limit per
+// workgroup, and no more than a launch gets without a function attribute. 0: the query failed.
+size_t hwc_lds_limit() {
+  int dev = 0, per_block = 0;
+  if (hipGetDevice(&dev) != hipSuccess ||
+      hipDeviceGetAttribute(&per_block, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess || per_block <= 0)
+    return 0;
+  return static_cast<size_t>(per_block) < kPlainLdsBytes ? static_cast<size_t>(per_block) : kPlainLdsBytes;
+}
+
 template <typename Tin>
 int launch_hwc(void* dst, int32_t out_dt, const void* src, int64_t batch, int64_t pixels, int32_t channels,
                const RowIndex& ri, const Affine& aff, hipStream_t st) {
-  const int64_t tiles = (pixels + kPix - 1) / kPix;
-  const size_t lds = static_cast<size_t>(kPix) * channels * sizeof(Tin);
-  const dim3 grid(static_cast<uint32_t>(batch * tiles));
   if constexpr (sizeof(Tin) == 1) {
     if (channels == 3 && (out_dt == kBF16 || out_dt == kF32)) {
       const int64_t tiles3 = (pixels + kPix3 - 1) / kPix3;
@@ -194,14 +204,25 @@ int launch_hwc(void* dst, int32_t out_dt, const void* src, int64_t batch, int64_
       return static_cast<int>(hipGetLastError());
     }
   }
+  if (out_dt != kBF16 && out_dt != kF32) return -1;
+  // The tile is kPix pixels while that fits the LDS a workgroup may have (u8 and bf16 at every channel count,
+  // f32 up to 8 channels); wider pixels halve it (f32 x 16 channels: 512 pixels), so the request never
+  // passes the limit and no shape fails at launch.
+  const size_t px_bytes = static_cast<size_t>(channels) * sizeof(Tin);
+  const size_t limit = hwc_lds_limit();
+  int32_t tile_px = kPix;
+  while (tile_px > 8 && tile_px * px_bytes > limit) tile_px >>= 1;
+  if (tile_px * px_bytes > limit) return -5;  // not even 8 pixels fit (or no limit could be read)
+  const size_t lds = tile_px * px_bytes;
+  const int64_t tiles = (pixels + tile_px - 1) / tile_px;
+  if (batch * tiles >= (int64_t{1} << 32)) return -4;  // the grid is one block per (image, tile)
+  const dim3 grid(static_cast<uint32_t>(batch * tiles));
   if (out_dt == kBF16)
     hipLaunchKernelGGL((hwc_to_chw_kernel<Tin, 1>), grid, dim3(kThreads), lds, st, dst, static_cast<const Tin*>(src),
-                       pixels, channels, tiles, ri, aff);
-  else if (out_dt == kF32)
-    hipLaunchKernelGGL((hwc_to_chw_kernel<Tin, 0>), grid, dim3(kThreads), lds, st, dst, static_cast<const Tin*>(src),
-                       pixels, channels, tiles, ri, aff);
+                       pixels, channels, tiles, tile_px, ri, aff);
   else
-    return -1;
+    hipLaunchKernelGGL((hwc_to_chw_kernel<Tin, 0>), grid, dim3(kThreads), lds, st, dst, static_cast<const Tin*>(src),
+                       pixels, channels, tiles, tile_px, ri, aff);
   return static_cast<int>(hipGetLastError());
 }
 

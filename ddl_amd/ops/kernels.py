@@ -67,6 +67,11 @@ def _is_gpu(t) -> bool:
     return isinstance(t, HostRows) or (isinstance(t, torch.Tensor) and t.is_cuda)
 
 
+def _same_device(out: torch.Tensor, src) -> bool:
+    """``out`` can take a kernel's result for ``src``: on the source tensor's GPU (any GPU for host-mapped rows)."""
+    return out.is_cuda and (isinstance(src, HostRows) or out.device == src.device)
+
+
 def _src_addr(src) -> int:
     return src.device_ptr if isinstance(src, HostRows) else src.data_ptr()
 
@@ -79,6 +84,8 @@ def _index_kw(index: torch.Tensor | None, perm: FeistelPermutation | None, base:
             raise TypeError("index must be int64")
         if not index.is_cuda:
             raise ValueError("index must live on the GPU for a GPU gather")
+        if not index.is_contiguous():
+            raise ValueError("index must be contiguous")
         return dict(mode=1, idx=index.data_ptr(), base=0, keys=[0] * 6, n_domain=1, half_bits=1)
     if perm is not None:
         return dict(mode=2, idx=0, base=int(base), **perm.device_args())
@@ -175,7 +182,8 @@ def gather_rows(src, index: torch.Tensor | None = None, *, perm: FeistelPermutat
         raise ValueError("gather_rows: source must be contiguous")
     if out is None:
         out = torch.empty((n_rows,) + row_shape, dtype=out_dtype, device=src.device)
-    elif not out.is_contiguous() or out.dtype != out_dtype or out.numel() != n_rows * row_elems:
+    elif (not out.is_contiguous() or out.dtype != out_dtype or out.numel() != n_rows * row_elems
+          or not _same_device(out, src)):
         raise ValueError("gather_rows: bad out tensor")
     sc, bi = _affine_lists(scale, bias)
     if sc and plane is None:
@@ -203,7 +211,9 @@ def scatter_rows(dst: torch.Tensor, src: torch.Tensor, index: torch.Tensor, *, s
     if not dst.is_cuda:
         dst.index_copy_(0, index.to(torch.int64), src)
         return dst
-    row_elems = int(math.prod(src.shape[1:])) if src.dim() > 1 else 1
+    if src.device != dst.device or not dst.is_contiguous() or not src.is_contiguous():
+        raise ValueError("scatter_rows: dst and src must be contiguous tensors on one device")
+    row_elems =int(math.prod(src.shape[1:])) if src.dim() > 1 else 1
     _native.hip().gather_rows(
         dst=dst.data_ptr(), out_dt=_dtypes.code(dst.dtype), src=src.data_ptr(), in_dt=_dtypes.code(src.dtype),
         n_rows=src.shape[0], row_elems=row_elems, scale=[], bias=[], plane=0, scatter=True,
@@ -356,12 +366,24 @@ def collate_hwc_to_chw(src, index: torch.Tensor | None = None, *, perm: FeistelP
     spatial = tuple(src.shape[1:-1])
     pixels = int(math.prod(spatial))
     sc, bi = norm_affine(c, mean, std, scale, bias, pixel_max(src.dtype))
+    if isinstance(src, torch.Tensor) and not src.is_contiguous():
+        raise ValueError("collate_hwc_to_chw: source must be contiguous")
     if out is None:
         out = torch.empty((n_rows, c) + spatial, dtype=out_dtype, device=src.device)
-    _native.hip().collate_hwc_to_chw(
-        dst=out.data_ptr(), out_dt=_dtypes.code(out_dtype), src=_src_addr(src), in_dt=_dtypes.code(src.dtype),
-        batch=n_rows, pixels=pixels, channels=c, scale=sc, bias=bi, stream=_stream_handle(stream),
-        **_index_kw(index, perm, base))
+    elif (not out.is_contiguous() or out.dtype != out_dtype or out.numel() != n_rows * c * pixels
+          or not _same_device(out, src)):
+        raise ValueError(f"collate_hwc_to_chw: out must be a contiguous {out_dtype} tensor of "
+                         f"{n_rows * c * pixels} elements on {src.device}")
+    try:
+        _native.hip().collate_hwc_to_chw(
+            dst=out.data_ptr(), out_dt=_dtypes.code(out_dtype), src=_src_addr(src), in_dt=_dtypes.code(src.dtype),
+            batch=n_rows, pixels=pixels, channels=c, scale=sc, bias=bi, stream=_stream_handle(stream),
+            **_index_kw(index, perm, base))
+    except ValueError as e:
+        if "(code -5)" not in str(e):
+            raise
+        # the kernel stages whole pixels in LDS: 8 of them must fit a workgroup's share
+        raise ValueError(f"collate_hwc_to_chw: {c} channels of {src.dtype} do not fit the LDS tile") from e
     return out
 
 
