@@ -52,11 +52,21 @@ def main(argv=None):
                          "(ResidentTokenLoader; also reports host_us_per_step and kernel_us)")
     ap.add_argument("--kernel-sample", type=int, default=16,
                     help="resident: device events around the pack launch of every N-th step (kernel_us; 0 = none)")
+    ap.add_argument("--plan", default="host", choices=["host", "device"],
+                    help="resident: where a batch's order and pack plan are built. device: descriptor, plan and pack "
+                         "are launches, with no host planning (in-order packing, fixed rows; the batch's counts "
+                         "are device scalars)")
     ap.add_argument("--max-blocks", type=int, default=None,
                     help="zerocopy: grid cap of the gather kernel (0 = uncapped; default: the loader's)")
     a = ap.parse_args(argv)
     zc = a.path in ("zerocopy", "resident")  # producer-free paths
     resident = a.path == "resident"
+    if a.plan != "host" and not resident:
+        ap.error("--plan device needs --path resident")
+    if a.plan == "device" and a.mode == "pack":
+        if a.pack_order != "in_order":
+            ap.error("--plan device builds the in-order plan: pass --pack-order in_order")
+        a.token_rows = "fixed"
 
     import torch
     import torch.distributed as dist
@@ -101,7 +111,7 @@ def main(argv=None):
             pack_order = a.pack_order if a.mode == "pack" else "in_order"
             if resident:
                 dl = ddl_amd.ResidentTokenLoader(source, gb, a.seq_len, a.mode, env, pack_order=pack_order,
-                                                 token_rows=a.token_rows, n_epochs=n_epochs)
+                                                 token_rows=a.token_rows, n_epochs=n_epochs, plan=a.plan)
                 dl.profile_every = a.kernel_sample
             elif zc:
                 dl = ddl_amd.ZeroCopyTokenLoader(source, gb, a.seq_len, a.mode, env, pack_order=pack_order,
@@ -137,13 +147,26 @@ def main(argv=None):
                 dist.barrier(group=env.control_group)
             t0 = time.perf_counter()
             rows = 0
+            dev_counts = None  # plan="device": the counts are device scalars, summed there and read once
             for _ in range(a.steps):
                 b = next(it)
                 acc.add(b["input_ids"])
+                if torch.is_tensor(b["n_tokens"]):
+                    if dev_counts is None:
+                        dev_counts = torch.zeros(2, dtype=torch.int64, device=b["n_tokens"].device)
+                    dev_counts[0].add_(b["n_tokens"])
+                    if "n_rows" in b:
+                        dev_counts[1].add_(b["n_rows"])
+                    else:
+                        rows += b["input_ids"].shape[0]
+                    continue
                 rows += b.get("n_rows", b["input_ids"].shape[0])
                 real += b["n_tokens"]  # counted from the delivered batches (producer tag), not estimated
             sync()
             dt = time.perf_counter() - t0
+            if dev_counts is not None:
+                real += int(dev_counts[0])
+                rows += int(dev_counts[1])
             st = dl.stats()
             timing = dl.timing() if resident else None  # of the measured phase and its warm-up
             if resident:
@@ -194,7 +217,7 @@ def main(argv=None):
                                 "kernel_us": None if timing["kernel_us"] is None else round(timing["kernel_us"], 1),
                                 "kernel_samples": timing["kernel_samples"],
                                 "load_s": round(st["load_s"], 3), "load_gbps": round(st["load_gbps"], 2),
-                                "replica_shared": st["replica_shared"]}
+                                "replica_shared": st["replica_shared"], "plan": a.plan}
                 elif zc:
                     per_path = {"path": "zerocopy", "max_blocks": st["max_blocks"], "host_waits": st["host_waits"],
                                 "prefault_s": round(st["prefault_s"], 3)}

@@ -340,8 +340,124 @@ def tokens_indexed(dev, repeats=5) -> None:
         "fused_tokens_per_s": round(T_mean / med["fused"], 1)}), flush=True)
 
 
+def tokens_plan(dev, repeats=5) -> None:
+    """The device-built batch plan at the ``tokens_indexed`` shape (uint16 corpus of 131072 sequences, 2048
+    sequences per batch, seq_len 4096, pack, fixed rows): ``token_batch_descriptor`` + ``pack_plan_device`` -- one
+    workgroup each, added to every ``plan="device"`` step -- and the pack kernel reading the plan's counts from
+    device memory, against the same kernel under the host plan (descriptor already on the device). 4 batches
+    (positions of one Feistel order, own plan arrays, own outputs) are issued round-robin at launcher level, so
+    the times are device times. The outputs of the two routes are compared first."""
+    from ddl_amd import _native
+    from ddl_amd.ops.kernels import (_index_kw, carve_token_outputs, device_batch_bytes, device_plan_bytes,
+                                     launch_device_plan, segment_sources, token_output_bytes)
+
+    hip = _native.hip()
+    rng = np.random.default_rng(0)
+    n_src, B, S, rot = 131072, 2048, 4096, 4
+    lens = rng.integers(256, 4097, size=n_src)
+    offs = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    corpus = torch.randint(0, 32768, (int(offs[-1]),), dtype=torch.int16, device=dev)
+    coffs = torch.from_numpy(offs).to(dev)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    perm = FeistelPermutation(n_src, 3, 1)
+    M = R = B  # the loader's capacities: layout.max_segments = B * ceil(max_len / S)
+    plan_b = device_plan_bytes(B, M, R)
+    cases = []
+    for k in range(rot):
+        idx = perm(np.arange(k * B, (k + 1) * B, dtype=np.int64))
+        start = np.ascontiguousarray(offs[idx])
+        dofs = np.concatenate([[0], np.cumsum(offs[idx + 1] - offs[idx])]).astype(np.int64)
+        rs, re_, so = ops.pack_plan(dofs, S)
+        n_rows, n_seg, T = len(rs), len(so) - 1, int(dofs[-1])
+        seg_src = np.ascontiguousarray(segment_sources(start, dofs, so, n_seg))
+        d = {k_: torch.from_numpy(v).to(dev) for k_, v in dict(start=start, rs=rs, re=re_, so=so,
+                                                               seg_src=seg_src).items()}
+        host_out = carve_token_outputs(torch.empty(token_output_bytes(R, S, n_seg), dtype=torch.uint8, device=dev),
+                                       R, S, n_seg)
+        plan = torch.empty(plan_b, dtype=torch.uint8, device=dev)
+        whole = torch.empty(device_batch_bytes(R, S, M), dtype=torch.uint8, device=dev)
+        cases.append(dict(d=d, host_out=host_out, plan=plan, whole=whole, n_rows=n_rows, n_seg=n_seg, T=T,
+                          sel=_index_kw(None, perm, k * B)))
+
+    def device_route(c):
+        return launch_device_plan(c["plan"].data_ptr(), c["whole"], corpus_ptr=corpus.data_ptr(),
+                                  corpus_elems=corpus.numel(), tok16=True, corpus_offsets_ptr=coffs.data_ptr(),
+                                  n_corpus=n_src, selector=c["sel"], n=B, seq_len=S, pad_id=0, pack=True, max_segs=M,
+                                  max_rows=R, stream=stream)
+
+    def host_pack(c):
+        d = c["d"]
+        ids, mask, pos, seg, cu = c["host_out"]
+        hip.pad_pack_tokens_indexed(corpus=corpus.data_ptr(), corpus_elems=corpus.numel(),
+                                    src_start=d["start"].data_ptr(), seg_src=d["seg_src"].data_ptr(), offsets=0,
+                                    row_start=d["rs"].data_ptr(), row_end=d["re"].data_ptr(),
+                                    seg_offsets=d["so"].data_ptr(), n_seg=c["n_seg"], rows=c["n_rows"], seq_len=S,
+                                    pad_id=0, mode=1, stream=stream, tok16=True, fill_rows=R,
+                                    out_tokens=ids.data_ptr(), attn_mask=mask.data_ptr(), position_ids=pos.data_ptr(),
+                                    pos_is_i64=True, segment_ids=seg.data_ptr(), cu_seqlens_out=cu.data_ptr())
+
+    for c in cases:  # the two routes write the same bytes
+        r = device_route(c)
+        host_pack(c)
+        torch.cuda.synchronize()
+        ids, mask, pos, seg, cu = c["host_out"]
+        assert r["counts"].tolist()[:3] == [c["n_rows"], c["n_seg"], c["T"]], "device and host plans differ"
+        assert all(torch.equal(a, b) for a, b in zip((r["input_ids"], r["attention_mask"], r["position_ids"],
+                                                      r["segment_ids"]), (ids, mask, pos, seg))), "outputs differ"
+        assert torch.equal(r["cu_seqlens"][:c["n_seg"] + 1], cu)
+        assert bool((r["cu_seqlens"][c["n_seg"]:] == c["T"]).all())
+        # the three launches of the device route, one by one, on this batch's own arrays
+        p, n = c["plan"].data_ptr(), B
+        a16 = lambda v: -(-v // 16) * 16  # noqa: E731
+        o_off = p + a16(8 * n)
+        o_ss = o_off + a16(8 * (n + 1))
+        o_so = o_ss + a16(8 * M)
+        o_rs = o_so + a16(8 * (M + 1))
+        o_re = o_rs + a16(8 * R)
+        o_scr = o_re + a16(8 * R)
+        cp = r["counts"].data_ptr()
+        c["descriptor"] = lambda p=p, o_off=o_off, o_ss=o_ss, cp=cp, sel=c["sel"]: hip.token_batch_descriptor(
+            corpus_offsets=coffs.data_ptr(), n_corpus=n_src, n=B, seq_len=S, max_segs=M, src_start=p, offsets=o_off,
+            seg_src=o_ss, counts=cp, pad_counts=False, stream=stream, **sel)
+        c["plan_kernel"] = lambda o_off=o_off, o_so=o_so, o_rs=o_rs, o_re=o_re, o_scr=o_scr, cp=cp: (
+            hip.pack_plan_device)(
+            offsets=o_off, n=B, seq_len=S, max_segs=M, max_rows=R, seg_offsets=o_so, row_start=o_rs, row_end=o_re,
+            counts=cp, scratch=o_scr, stream=stream)
+        c["device_pack"] = lambda p=p, o_ss=o_ss, o_so=o_so, o_rs=o_rs, o_re=o_re, cp=cp, r=r: (
+            hip.pad_pack_tokens_indexed)(
+            corpus=corpus.data_ptr(), corpus_elems=corpus.numel(), src_start=p, seg_src=o_ss, offsets=0,
+            row_start=o_rs, row_end=o_re, seg_offsets=o_so, n_seg=0, rows=0, seq_len=S, pad_id=0, mode=1,
+            stream=stream, tok16=True, fill_rows=R, dev_counts=cp, cu_cap=M, out_tokens=r["input_ids"].data_ptr(),
+            attn_mask=r["attention_mask"].data_ptr(), position_ids=r["position_ids"].data_ptr(), pos_is_i64=True,
+            segment_ids=r["segment_ids"].data_ptr(), cu_seqlens_out=r["cu_seqlens"].data_ptr())
+    runs = []
+    for rep in range(repeats):
+        t = {"descriptor": rotating([c["descriptor"] for c in cases]),
+             "pack_plan": rotating([c["plan_kernel"] for c in cases]),
+             "device_counts_pack": rotating([c["device_pack"] for c in cases]),
+             "host_plan_pack": rotating([lambda c=c: host_pack(c) for c in cases]),
+             "device_route": rotating([lambda c=c: device_route(c) for c in cases])}
+        runs.append(t)
+        print(json.dumps({"kernel": "tokens_plan", "repeat": rep,
+                          **{k + "_us": round(v * 1e6, 2) for k, v in t.items()}}), flush=True)
+    med = {k: float(np.median([t[k] for t in runs])) for k in runs[0]}
+    T_mean = float(np.mean([c["T"] for c in cases]))
+    print(json.dumps({
+        "kernel": "tokens_plan summary", "sequences": B, "seq_len": S, "token_dtype": "uint16", "rows": R,
+        "max_segs": M, "tokens": T_mean, "repeats": repeats,
+        **{k + "_us_median": round(v * 1e6, 2) for k, v in med.items()},
+        **{k + "_us_min_max": [round(min(t[k] for t in runs) * 1e6, 2), round(max(t[k] for t in runs) * 1e6, 2)]
+           for k in med},
+        "descriptor_plus_plan_us_median": round((med["descriptor"] + med["pack_plan"]) * 1e6, 2),
+        "device_route_tokens_per_s": round(T_mean / med["device_route"], 1),
+        "host_plan_pack_tokens_per_s": round(T_mean / med["host_plan_pack"], 1)}), flush=True)
+
+
 if __name__ == "__main__":
     if "--only-tokens-indexed" in sys.argv[1:]:  # the one case, e.g. for profiles/resident_tokens/
         tokens_indexed(torch.device("cuda", 0))
+        sys.exit(0)
+    if "--only-tokens-plan" in sys.argv[1:]:  # profiles/resident_tokens_plan/
+        tokens_plan(torch.device("cuda", 0))
         sys.exit(0)
     sys.exit(main())

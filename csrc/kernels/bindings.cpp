@@ -740,10 +740,12 @@ PYBIND11_MODULE(_ddl_hip, m) {
       [](uintptr_t corpus, int64_t corpus_elems, uintptr_t src_start, uintptr_t seg_src, uintptr_t offsets,
          uintptr_t row_start, uintptr_t row_end, uintptr_t seg_offsets, int64_t n_seg, uintptr_t out_tokens,
          uintptr_t attn_mask, uintptr_t position_ids, bool pos_is_i64, uintptr_t segment_ids, uintptr_t cu_seqlens_out,
-         int64_t rows, int64_t seq_len, int pad_id, int mode, uintptr_t stream, int64_t fill_rows, bool tok16) {
+         int64_t rows, int64_t seq_len, int pad_id, int mode, uintptr_t stream, int64_t fill_rows, bool tok16,
+         uintptr_t dev_counts, int64_t cu_cap) {
         ddl::TokenSpec sp{};
         sp.tok16 = tok16 ? 1 : 0;
         sp.fill_rows = fill_rows;
+        sp.dev_counts = as_ptr<const int64_t>(dev_counts);
         sp.offsets = as_ptr<const int64_t>(offsets);
         sp.row_start = as_ptr<const int64_t>(row_start);
         sp.row_end = as_ptr<const int64_t>(row_end);
@@ -761,14 +763,38 @@ PYBIND11_MODULE(_ddl_hip, m) {
         sp.mode = mode;
         check_rc(ddl::pad_pack_tokens_indexed(sp, as_ptr<const void>(corpus), corpus_elems,
                                               as_ptr<const int64_t>(src_start), as_ptr<const int64_t>(seg_src),
-                                              as_stream(stream)),
+                                              as_stream(stream), cu_cap),
                  "pad_pack_tokens_indexed");
       },
       py::arg("corpus"), py::arg("corpus_elems"), py::arg("src_start"), py::arg("seg_src"), py::arg("offsets"),
       py::arg("row_start"), py::arg("row_end"), py::arg("seg_offsets"), py::arg("n_seg"), py::arg("out_tokens"),
       py::arg("attn_mask"), py::arg("position_ids"), py::arg("pos_is_i64"), py::arg("segment_ids"),
       py::arg("cu_seqlens_out"), py::arg("rows"), py::arg("seq_len"), py::arg("pad_id"), py::arg("mode"),
-      py::arg("stream"), py::arg("fill_rows") = 0, py::arg("tok16") = false);
+      py::arg("stream"), py::arg("fill_rows") = 0, py::arg("tok16") = false, py::arg("dev_counts") = 0,
+      py::arg("cu_cap") = 0);
+  m.def(
+      "token_batch_descriptor",
+      [](uintptr_t corpus_offsets, int64_t n_corpus, int mode, uintptr_t idx, int64_t base, std::vector<uint64_t> keys,
+         uint64_t n_domain, uint32_t half_bits, int64_t n, int64_t seq_len, int64_t max_segs, uintptr_t src_start,
+         uintptr_t offsets, uintptr_t seg_src, uintptr_t counts, bool pad_counts, uintptr_t stream) {
+        ddl::BatchDescSpec sp{};
+        sp.corpus_offsets = as_ptr<const int64_t>(corpus_offsets);
+        sp.n_corpus = n_corpus;
+        sp.ri = make_index(mode, idx, base, keys, n_domain, half_bits);
+        sp.n = n;
+        sp.seq_len = seq_len;
+        sp.max_segs = max_segs;
+        sp.src_start = as_ptr<int64_t>(src_start);
+        sp.offsets = as_ptr<int64_t>(offsets);
+        sp.seg_src = as_ptr<int64_t>(seg_src);
+        sp.counts = as_ptr<int64_t>(counts);
+        sp.pad_counts = pad_counts ? 1 : 0;
+        check_rc(ddl::token_batch_descriptor(sp, as_stream(stream)), "token_batch_descriptor");
+      },
+      py::arg("corpus_offsets"), py::arg("n_corpus"), py::arg("mode"), py::arg("idx"), py::arg("base"), py::arg("keys"),
+      py::arg("n_domain"), py::arg("half_bits"), py::arg("n"), py::arg("seq_len"), py::arg("max_segs"),
+      py::arg("src_start"), py::arg("offsets"), py::arg("seg_src"), py::arg("counts"), py::arg("pad_counts"),
+      py::arg("stream"));
   m.attr("TOKEN_SEG_LDS_CAP") = ddl::kTiSegCap;
   m.attr("RAGGED_MAP_CAP") = ddl::kRaggedMapCap;
   m.def(

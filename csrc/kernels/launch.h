@@ -134,11 +134,42 @@ int pad_pack_tokens_multi(const TokenSpec* specs, int n, hipStream_t st);
 // read from the corpus (HBM) instead: spec.tokens is null, the plan arrays (offsets [B + 1] in pad mode,
 // row_start / row_end / seg_offsets in pack mode) are positions of that virtual stream as for pad_pack_tokens.
 // corpus: int32, or uint16 when spec.tok16, corpus_elems elements; src_start [B] (pad mode) and seg_src
-// [n_seg] (pack mode: the corpus element of each segment's first token) are device-readable. A plan built on
-// the device (dev_counts) is not supported. Outputs of a row width that is a multiple of 4 must be 16-byte
-// aligned (the mask 4-byte). Block 0 writes cu_seqlens_out even when there is no row.
+// [n_seg] (pack mode: the corpus element of each segment's first token) are device-readable. Outputs of a row
+// width that is a multiple of 4 must be 16-byte aligned (the mask 4-byte). Block 0 writes cu_seqlens_out even
+// when there is no row.
+// A plan built on the device (pack mode, spec.dev_counts = pack_plan_device's counts): the kernel reads
+// {n_rows, n_seg} there instead of spec.rows / spec.n_seg, the grid is sized by spec.fill_rows (> 0, the plan's
+// row capacity) and n_rows < 0, an overflowed plan, writes every row as padding.
+// cu_cap > 0: cu_seqlens_out holds cu_cap + 1 entries, and the entries (n_seg, cu_cap] are written as
+// seg_offsets[n_seg], the token count: a fixed-capacity cu_seqlens describes zero-length trailing sequences.
 int pad_pack_tokens_indexed(const TokenSpec& spec, const void* corpus, int64_t corpus_elems, const int64_t* src_start,
-                            const int64_t* seg_src, hipStream_t st);
+                            const int64_t* seg_src, hipStream_t st, int64_t cu_cap = 0);
+
+// tokens_plan.hip -----------------------------------------------------------
+// The descriptor of a token batch, built on the device (one workgroup): sequence i of the batch is corpus
+// sequence q_i = source_row(ri, i) (identity base + i, an explicit device index, or the Feistel permutation
+// of position base + i), i.e. corpus elements [corpus_offsets[q_i], corpus_offsets[q_i + 1]). Writes what
+// pack_plan_device and pad_pack_tokens_indexed take: src_start [n], offsets [n + 1] (the exclusive scan of the
+// lengths: the virtual flat stream) and seg_src [max_segs] (segment j of sequence i = src_start[i] + j *
+// seq_len, numbered by the exclusive scan of ceil(len_i / seq_len) as pack_plan_device numbers seg_offsets),
+// counts[2] = the token count and counts[3] = the longest segment, min(max len, seq_len). counts[0 .. 1] are
+// pack_plan_device's; pad_counts != 0 (no plan follows) writes them as {n, 0}. Segments past max_segs are not
+// written (pack_plan_device reports the overflow); an index outside [0, n_corpus) is an empty sequence.
+struct BatchDescSpec {
+  const int64_t* corpus_offsets;  // [n_corpus + 1], device
+  int64_t n_corpus;
+  RowIndex ri;
+  int64_t n;
+  int64_t seq_len;
+  int64_t max_segs;
+  int64_t* src_start;
+  int64_t* offsets;
+  int64_t* seg_src;
+  int64_t* counts;  // [4]
+  int32_t pad_counts;
+  int32_t pad;
+};
+int token_batch_descriptor(const BatchDescSpec& spec, hipStream_t st);
 
 // ragged.hip ----------------------------------------------------------------
 // Device twin of the host gather_ragged: sequence i (src_start[i] elements into src, dst_offsets[i + 1] -

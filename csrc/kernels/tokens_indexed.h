@@ -40,6 +40,10 @@ DDL_TI_HD int64_t ti_grid(int64_t rows, int64_t fill_rows, int64_t seq_len, bool
   return g == 0 && has_cu ? 1 : g;
 }
 
+// block 0 copies seg_offsets[0 .. n] into cu_seqlens: n = n_seg, held inside the capacity where one is given
+// (cu_cap > 0: cu_seqlens has cu_cap + 1 entries; the entries (n, cu_cap] are then written as seg_offsets[n])
+DDL_TI_HD int64_t ti_cu_entries(int64_t n_seg, int64_t cu_cap) { return cu_cap > 0 && n_seg > cu_cap ? cu_cap : n_seg; }
+
 // workgroup bx, lane tid -> row and the lane's first position
 DDL_TI_HD void ti_lane_origin(uint32_t bx, int32_t chunks, int tid, int64_t* row, int64_t* p0) {
   const uint32_t r = bx / static_cast<uint32_t>(chunks);

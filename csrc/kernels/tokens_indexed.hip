@@ -21,7 +21,11 @@
 // Bounded writes: workgroup (row, chunk) writes positions [chunk * 512, min((chunk + 1) * 512, S)) of row
 // `row` < max(rows, fill_rows) of every output, each exactly once (the vector path only where all 4 positions
 // are inside the row), so every element of every [R, S] output is written once and nothing outside;
-// cu_seqlens_out[0 .. n_seg] is written by block 0.
+// cu_seqlens_out[0 .. n_seg] is written by block 0, and with a capacity (cu_cap) also (n_seg, cu_cap].
+// A plan built on the device (dev_counts, pack mode): rows and n_seg are two block-uniform loads of the plan's
+// counts, clamped as pad_pack_block (tokens.hip) clamps them -- a negative row count, an overflowed plan, makes
+// every row padding; the grid covers fill_rows, the plan's row capacity, and pack_plan_device never reports
+// more rows or segments than its capacities, which are the sizes of row_start / row_end / seg_offsets / seg_src.
 #include "common.h"
 #include "launch.h"
 #include "tokens_indexed.h"
@@ -35,6 +39,7 @@ struct IndexedSpec {
   int64_t corpus_elems;
   const int64_t* src_start;  // [B]: corpus element of each selected sequence
   const int64_t* seg_src;    // pack mode, [n_seg]: corpus element of each segment's first token
+  int64_t cu_cap;            // > 0: cu_seqlens_out holds cu_cap + 1 entries, those past n_seg = the token count
 };
 
 template <typename SegAt, typename SrcAt>
@@ -92,7 +97,12 @@ __device__ __forceinline__ void emit4_indexed(const IndexedSpec& ix, int64_t row
 __global__ void __launch_bounds__(kTiThreads) pad_pack_indexed_kernel(IndexedSpec ix, int32_t chunks) {
   __shared__ int64_t seg_lds[kTiSegCap];
   __shared__ int64_t src_lds[kTiSegCap];
-  const TokenSpec& sp = ix.tok;
+  TokenSpec& sp = ix.tok;
+  if (sp.dev_counts != nullptr) {  // plan built on the device: its row / segment counts (block-uniform loads)
+    const int64_t n_rows = sp.dev_counts[0];
+    sp.rows = n_rows < 0 ? 0 : n_rows;
+    sp.n_seg = n_rows < 0 ? 0 : sp.dev_counts[1];
+  }
   int64_t row, p0;
   ti_lane_origin(blockIdx.x, chunks, static_cast<int>(threadIdx.x), &row, &p0);
   const bool live = row < (sp.fill_rows > sp.rows ? sp.fill_rows : sp.rows);  // data row or padding row
@@ -114,9 +124,15 @@ __global__ void __launch_bounds__(kTiThreads) pad_pack_indexed_kernel(IndexedSpe
       seg_lds[i] = sp.seg_offsets[i];
       if (i < sp.n_seg) src_lds[i] = ix.seg_src[i];
     }
-  if (sp.cu_seqlens_out != nullptr && blockIdx.x == 0)  // owned copy of the sequence starts (cu_seqlens)
-    for (int64_t i = threadIdx.x; i <= sp.n_seg; i += kTiThreads)
+  if (sp.cu_seqlens_out != nullptr && blockIdx.x == 0) {  // owned copy of the sequence starts (cu_seqlens)
+    const int64_t n_cu = ti_cu_entries(sp.n_seg, ix.cu_cap);
+    for (int64_t i = threadIdx.x; i <= n_cu; i += kTiThreads)
       sp.cu_seqlens_out[i] = static_cast<int32_t>(sp.seg_offsets[i]);
+    if (ix.cu_cap > n_cu) {  // the tail of a fixed-capacity cu_seqlens: zero-length sequences at the token count
+      const int32_t total = static_cast<int32_t>(sp.seg_offsets[n_cu]);
+      for (int64_t i = n_cu + 1 + threadIdx.x; i <= ix.cu_cap; i += kTiThreads) sp.cu_seqlens_out[i] = total;
+    }
+  }
   __syncthreads();
   if (!live || p0 >= sp.seq_len) return;
   if (staged)
@@ -130,10 +146,15 @@ __global__ void __launch_bounds__(kTiThreads) pad_pack_indexed_kernel(IndexedSpe
 }  // namespace
 
 int pad_pack_tokens_indexed(const TokenSpec& spec, const void* corpus, int64_t corpus_elems, const int64_t* src_start,
-                            const int64_t* seg_src, hipStream_t st) {
-  if (spec.seq_len <= 0 || spec.rows < 0 || spec.n_seg < 0 || corpus_elems < 0) return -2;
-  if (spec.tokens != nullptr || spec.dev_counts != nullptr) return -2;  // the corpus is the only source; host plan
+                            const int64_t* seg_src, hipStream_t st, int64_t cu_cap) {
+  if (spec.seq_len <= 0 || spec.rows < 0 || spec.n_seg < 0 || corpus_elems < 0 || cu_cap < 0) return -2;
+  if (spec.tokens != nullptr) return -2;  // the corpus is the only source
   if (spec.mode != 0 && spec.mode != 1) return -2;
+  const bool dev_plan = spec.dev_counts != nullptr;
+  if (dev_plan) {  // rows and n_seg are the device's: every array the kernel may then read must be there
+    if (spec.mode != 1 || spec.fill_rows <= 0 || !corpus) return -2;
+    if (!spec.row_start || !spec.row_end || !spec.seg_offsets || !seg_src) return -2;
+  }
   if ((spec.rows > 0 || spec.fill_rows > 0) && !spec.out_tokens) return -2;
   if (spec.rows > 0) {
     if (!corpus) return -2;
@@ -150,10 +171,10 @@ int pad_pack_tokens_indexed(const TokenSpec& spec, const void* corpus, int64_t c
         reinterpret_cast<uintptr_t>(spec.segment_ids) % 16 || reinterpret_cast<uintptr_t>(spec.attn_mask) % 4)
       return -2;
   }
-  const int64_t grid = ti_grid(spec.rows, spec.fill_rows, spec.seq_len, has_cu);
+  const int64_t grid = ti_grid(dev_plan ? 0 : spec.rows, spec.fill_rows, spec.seq_len, has_cu);
   if (grid < 0) return -4;
   if (grid == 0) return 0;
-  IndexedSpec ix{spec, corpus, corpus_elems, src_start, seg_src};
+  IndexedSpec ix{spec, corpus, corpus_elems, src_start, seg_src, has_cu ? cu_cap : 0};
   if (spec.mode == 0 || !has_cu) ix.tok.cu_seqlens_out = nullptr;
   hipLaunchKernelGGL(pad_pack_indexed_kernel, dim3(static_cast<uint32_t>(grid)), dim3(kTiThreads), 0, st, ix,
                      static_cast<int32_t>(ti_chunks(spec.seq_len)));

@@ -978,6 +978,217 @@ def pack_tokens_indexed(corpus: torch.Tensor, corpus_offsets, idx, seq_len: int,
     return ids, mask, pos, seg, cu
 
 
+# ------------------------------- tokens out of an HBM corpus, planned on the device
+def device_plan_bytes(n: int, max_segs: int | None = None, max_rows: int = 0) -> int:
+    """Bytes of the plan arrays the device-planned ops keep between their launches (``max_segs`` None: pad mode):
+    src_start [n], offsets [n + 1], and in pack mode seg_src [max_segs], seg_offsets [max_segs + 1], row_start /
+    row_end [max_rows] and the plan kernel's scratch. Nothing a caller holds lives here."""
+    total = _align16(8 * n) + _align16(8 * (n + 1))
+    if max_segs is not None:
+        total += (_align16(8 * max_segs) + _align16(8 * (max_segs + 1)) + 2 * _align16(8 * max_rows)
+                  + _align16(4 * (2 * (max_segs + 1) + max_rows + 1)))  # == pack_plan_scratch_ints
+    return total
+
+
+def device_batch_bytes(rows: int, seq_len: int, max_segs: int | None = None, position_dtype=torch.int64) -> int:
+    """Bytes of what a device-planned batch hands to its caller: ``token_output_bytes`` (``cu_seqlens`` of
+    capacity ``max_segs`` + 1 in pack mode) and the four int64 counts behind it."""
+    return token_output_bytes(rows, seq_len, max_segs, position_dtype) + 32
+
+
+def launch_device_plan(plan_ptr: int, whole: torch.Tensor, *, corpus_ptr: int, corpus_elems: int, tok16: bool,
+                       corpus_offsets_ptr: int, n_corpus: int, selector: dict, n: int, seq_len: int, pad_id: int,
+                       pack: bool, max_segs: int = 0, max_rows: int = 0, position_dtype=torch.int64,
+                       stream: int = 0) -> dict:
+    """The launches of one device-planned batch on raw stream ``stream``: descriptor, (pack mode) plan, pack.
+    ``plan_ptr``: ``device_plan_bytes`` of 16-byte aligned device memory for the plan arrays; ``whole``:
+    ``device_batch_bytes`` of uint8 device memory the outputs and the counts are carved from; ``selector``: the
+    ``mode / idx / base / keys / n_domain / half_bits`` of a ``RowIndex``. Nothing here allocates, copies or
+    synchronises. Returns the dict of ``pack_tokens_indexed_device`` / ``pad_tokens_indexed_device``."""
+    h = _native.hip()
+    n, S, R, M = int(n), int(seq_len), int(max_rows), int(max_segs)
+    o_src = plan_ptr
+    o_off = o_src + _align16(8 * n)
+    o_end = o_off + _align16(8 * (n + 1))
+    i64 = position_dtype == torch.int64
+    if not pack:
+        out_b = token_output_bytes(n, S, None, position_dtype)
+        ids, mask, pos, _, _ = carve_token_outputs(whole, n, S, None, position_dtype)
+        counts = whole[out_b:out_b + 32].view(torch.int64)
+        h.token_batch_descriptor(corpus_offsets=corpus_offsets_ptr, n_corpus=n_corpus, n=n, seq_len=S, max_segs=0,
+                                 src_start=o_src, offsets=o_off, seg_src=0, counts=counts.data_ptr(),
+                                 pad_counts=True, stream=stream, **selector)
+        h.pad_pack_tokens_indexed(
+            corpus=corpus_ptr, corpus_elems=corpus_elems, src_start=o_src, seg_src=0, offsets=o_off, row_start=0,
+            row_end=0, seg_offsets=0, n_seg=0, out_tokens=ids.data_ptr(), attn_mask=mask.data_ptr(),
+            position_ids=pos.data_ptr(), pos_is_i64=i64, segment_ids=0, cu_seqlens_out=0, rows=n, seq_len=S,
+            pad_id=pad_id, mode=0, stream=stream, tok16=tok16)
+        return {"input_ids": ids, "attention_mask": mask, "position_ids": pos, "counts": counts}
+    o_ss = o_end
+    o_so = o_ss + _align16(8 * M)
+    o_rs = o_so + _align16(8 * (M + 1))
+    o_re = o_rs + _align16(8 * R)
+    o_scr = o_re + _align16(8 * R)
+    out_b = token_output_bytes(R, S, M, position_dtype)
+    ids, mask, pos, seg, cu = carve_token_outputs(whole, R, S, M, position_dtype)
+    counts = whole[out_b:out_b + 32].view(torch.int64)
+    c_ptr = counts.data_ptr()
+    h.token_batch_descriptor(corpus_offsets=corpus_offsets_ptr, n_corpus=n_corpus, n=n, seq_len=S, max_segs=M,
+                             src_start=o_src, offsets=o_off, seg_src=o_ss, counts=c_ptr, pad_counts=False,
+                             stream=stream, **selector)
+    h.pack_plan_device(offsets=o_off, n=n, seq_len=S, max_segs=M, max_rows=R, seg_offsets=o_so, row_start=o_rs,
+                       row_end=o_re, counts=c_ptr, scratch=o_scr, stream=stream)
+    h.pad_pack_tokens_indexed(
+        corpus=corpus_ptr, corpus_elems=corpus_elems, src_start=o_src, seg_src=o_ss, offsets=0, row_start=o_rs,
+        row_end=o_re, seg_offsets=o_so, n_seg=0, out_tokens=ids.data_ptr(), attn_mask=mask.data_ptr(),
+        position_ids=pos.data_ptr(), pos_is_i64=i64, segment_ids=seg.data_ptr(), cu_seqlens_out=cu.data_ptr(),
+        rows=0, seq_len=S, pad_id=pad_id, mode=1, stream=stream, fill_rows=R, tok16=tok16, dev_counts=c_ptr,
+        cu_cap=M)
+    return {"input_ids": ids, "attention_mask": mask, "position_ids": pos, "segment_ids": seg, "cu_seqlens": cu,
+            "counts": counts}
+
+
+def _device_plan_args(corpus, corpus_offsets, index, perm, base, count, seq_len, position_dtype):
+    """Checked (flat corpus, offsets, n) of a device-planned op."""
+    if position_dtype not in (torch.int64, torch.int32):
+        raise TypeError("position_dtype must be int64 or int32")
+    if not isinstance(corpus, torch.Tensor) or (corpus.dtype != torch.int32 and corpus.dtype not in _TOK16):
+        raise TypeError("corpus must be a flat int32 / 16-bit token tensor")
+    if not isinstance(corpus_offsets, torch.Tensor) or corpus_offsets.dtype != torch.int64:
+        raise TypeError("corpus_offsets must be an int64 tensor")
+    if not corpus.is_contiguous() or not corpus_offsets.is_contiguous():
+        raise ValueError("corpus and corpus_offsets must be contiguous")
+    if corpus_offsets.device != corpus.device:
+        raise ValueError("corpus_offsets must be on the corpus's device")
+    if int(seq_len) <= 0:
+        raise ValueError("seq_len must be > 0")
+    offs = corpus_offsets.reshape(-1)
+    if offs.numel() < 1:
+        raise ValueError("corpus_offsets needs at least one entry")
+    if index is not None and perm is not None:
+        raise ValueError("give either index or perm, not both")
+    if index is not None and (index.dtype != torch.int64 or index.device != corpus.device
+                              or not index.is_contiguous()):
+        raise ValueError("index must be a contiguous int64 tensor on the corpus's device")
+    if index is not None and count is not None and int(count) != index.numel():
+        raise ValueError("count does not match the index")
+    n_corpus = offs.numel() - 1
+    if index is not None:
+        n = index.numel()
+    elif count is not None:
+        n = int(count)
+    else:
+        n = (perm.n if perm is not None else n_corpus) - int(base)
+    if n < 0 or (index is None and int(base) < 0):
+        raise ValueError("negative base or count")
+    if perm is not None and (int(base) + n > perm.n or perm.n > n_corpus):
+        raise IndexError("perm positions out of range, or a permutation domain larger than the corpus")
+    if index is None and perm is None and int(base) + n > n_corpus:
+        raise IndexError("identity rows out of range")
+    return corpus.reshape(-1), offs, n
+
+
+def _device_plan_caps(n: int, corpus_elems: int, seq_len: int, max_rows, max_segs) -> tuple[int, int]:
+    """Default capacities: ``pack_capacity`` of ``n`` sequences that hold at most the whole corpus (true of any
+    selection without repeats; an index with repeats that carries more tokens than the corpus holds overflows
+    them, which the plan reports as ``counts[0] = -1``: pass capacities of your own)."""
+    cap_segs, cap_rows = pack_capacity(n, corpus_elems, seq_len)
+    M = max(cap_segs, 1) if max_segs is None else int(max_segs)
+    R = max(min(cap_rows, M), 1) if max_rows is None else int(max_rows)
+    if M < 1 or R < 1:
+        raise ValueError("max_segs and max_rows must be >= 1")
+    if M >= (1 << 31) - 1:
+        raise ValueError("max_segs does not fit the plan's int32 segment ids")
+    return M, R
+
+
+def _ref_selected(offs: torch.Tensor, n: int, index, perm, base) -> np.ndarray:
+    return _ref_rows(offs.numel() - 1, n, index, perm, int(base)).numpy()
+
+
+def pack_tokens_indexed_device(corpus: torch.Tensor, corpus_offsets: torch.Tensor, *,
+                               index: torch.Tensor | None = None, perm: FeistelPermutation | None = None,
+                               base: int = 0, count: int | None = None, seq_len: int, pad_id: int = 0,
+                               position_dtype=torch.int64, max_rows: int | None = None, max_segs: int | None = None,
+                               out: torch.Tensor | None = None, stream=None) -> dict:
+    """``pack_tokens_indexed`` with nothing computed on the host: ``corpus`` (flat int32 / 16-bit ids) and
+    ``corpus_offsets`` (int64 [n_corpus + 1]) are device tensors, and the sequences are selected as ``gather_rows``
+    selects rows -- a device ``index``, or positions ``[base, base + count)`` of ``perm`` (evaluated inline by the
+    kernel), or of the identity. Three launches, no copy and no synchronisation: ``token_batch_descriptor``
+    (src_start, running offsets, each segment's corpus element), ``pack_plan_device`` (the in-order plan and its
+    counts), and ``pad_pack_tokens_indexed`` reading the counts from device memory.
+
+    Shapes are static: ``max_rows`` rows (rows past the plan's are padding: pad_id, mask 0, position 0, segment
+    -1) and ``cu_seqlens`` of ``max_segs`` + 1 entries whose entries past ``n_seg`` equal the token count
+    (zero-length trailing sequences). Returns ``input_ids``, ``attention_mask``, ``position_ids``, ``segment_ids``,
+    ``cu_seqlens`` and ``counts`` = device int64 ``[n_rows, n_seg, n_tokens, max_seg]`` (``n_rows`` = -1 when a
+    capacity was too small: every row is then padding and ``cu_seqlens`` is all zero). ``out``: a uint8 device
+    buffer of ``device_plan_bytes(n, max_segs, max_rows) + device_batch_bytes(max_rows, seq_len, max_segs)``
+    bytes that everything is carved from, else one allocation. CPU tensors take the reference path
+    (``ref_gather_ragged`` + ``ref_pack_plan`` + ``ref_pack_tokens``): the same dict."""
+    flat, offs, n = _device_plan_args(corpus, corpus_offsets, index, perm, base, count, seq_len, position_dtype)
+    S = int(seq_len)
+    M, R = _device_plan_caps(n, flat.numel(), S, max_rows, max_segs)
+    if not flat.is_cuda:
+        tokens, dofs = ref_gather_ragged(flat, offs, _ref_selected(offs, n, index, perm, base))
+        rs, re_, so = ref_pack_plan(dofs.numpy(), S)
+        n_seg, n_tokens = len(so) - 1, int(dofs[-1])
+        ok = n_seg <= M and len(rs) <= R
+        keep = slice(None) if ok else slice(0, 0)
+        ids, mask, pos, seg = ref_pack_tokens(tokens, rs[keep], re_[keep], so, S, pad_id, position_dtype, fill_rows=R)
+        cu = torch.full((M + 1,), n_tokens if ok else 0, dtype=torch.int32)
+        if ok:
+            cu[:n_seg + 1] = torch.from_numpy(so.astype(np.int32))
+        max_seg = int(np.diff(so).max()) if n_seg else 0
+        counts = torch.tensor([len(rs) if ok else -1, n_seg, n_tokens, max_seg], dtype=torch.int64)
+        return {"input_ids": ids, "attention_mask": mask, "position_ids": pos, "segment_ids": seg, "cu_seqlens": cu,
+                "counts": counts}
+    plan_b = device_plan_bytes(n, M, R)
+    handle = _stream_handle(stream)
+    if isinstance(stream, int):
+        stream = torch.cuda.ExternalStream(stream, device=flat.device)
+    with torch.cuda.stream(stream):
+        buf = _token_out_buffer(out, plan_b + device_batch_bytes(R, S, M, position_dtype), flat.device)
+    return launch_device_plan(
+        buf.data_ptr(), buf[plan_b:], corpus_ptr=flat.data_ptr(), corpus_elems=flat.numel(),
+        tok16=flat.dtype in _TOK16, corpus_offsets_ptr=offs.data_ptr(), n_corpus=offs.numel() - 1,
+        selector=_index_kw(index, perm, base) if n else _index_kw(None, None, 0), n=n, seq_len=S, pad_id=pad_id,
+        pack=True, max_segs=M, max_rows=R,
+        position_dtype=position_dtype, stream=handle)
+
+
+def pad_tokens_indexed_device(corpus: torch.Tensor, corpus_offsets: torch.Tensor, *,
+                              index: torch.Tensor | None = None, perm: FeistelPermutation | None = None,
+                              base: int = 0, count: int | None = None, seq_len: int, pad_id: int = 0,
+                              position_dtype=torch.int64, out: torch.Tensor | None = None, stream=None) -> dict:
+    """``pad_tokens_indexed`` with nothing computed on the host (see ``pack_tokens_indexed_device``): two
+    launches, ``token_batch_descriptor`` and ``pad_pack_tokens_indexed``. Returns ``input_ids``,
+    ``attention_mask``, ``position_ids`` ([n, seq_len]) and ``counts`` = device int64 ``[n, 0, n_tokens,
+    max_seg]`` (``n_tokens``: the tokens of the selected sequences before truncation to ``seq_len``; ``max_seg``:
+    the longest row). ``out``: ``device_plan_bytes(n) + device_batch_bytes(n, seq_len)`` bytes. CPU tensors take
+    the reference path (``ref_gather_ragged`` + ``ref_pad_tokens``)."""
+    flat, offs, n = _device_plan_args(corpus, corpus_offsets, index, perm, base, count, seq_len, position_dtype)
+    S = int(seq_len)
+    if not flat.is_cuda:
+        tokens, dofs = ref_gather_ragged(flat, offs, _ref_selected(offs, n, index, perm, base))
+        ids, mask, pos = ref_pad_tokens(tokens, dofs, S, pad_id, position_dtype)
+        lens = np.diff(dofs.numpy())
+        counts = torch.tensor([n, 0, int(dofs[-1]), int(min(lens.max(), S)) if n else 0], dtype=torch.int64)
+        return {"input_ids": ids, "attention_mask": mask, "position_ids": pos, "counts": counts}
+    plan_b = device_plan_bytes(n)
+    handle = _stream_handle(stream)
+    if isinstance(stream, int):
+        stream = torch.cuda.ExternalStream(stream, device=flat.device)
+    with torch.cuda.stream(stream):
+        buf = _token_out_buffer(out, plan_b + device_batch_bytes(n, S, None, position_dtype), flat.device)
+    return launch_device_plan(
+        buf.data_ptr(), buf[plan_b:], corpus_ptr=flat.data_ptr(), corpus_elems=flat.numel(),
+        tok16=flat.dtype in _TOK16, corpus_offsets_ptr=offs.data_ptr(), n_corpus=offs.numel() - 1,
+        selector=_index_kw(index, perm, base) if n else _index_kw(None, None, 0), n=n, seq_len=S, pad_id=pad_id,
+        pack=False,
+        position_dtype=position_dtype, stream=handle)
+
+
 # ----------------------------------------------------------------- reductions
 def ref_checksum(x: torch.Tensor) -> int:
     b = x.detach().contiguous().reshape(-1).view(torch.uint8).cpu().numpy()

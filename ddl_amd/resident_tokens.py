@@ -23,6 +23,13 @@ The batches are those of the other two token paths, key by key, and the order an
 checkpoint are ``PrefetchedIndexedLoader``'s: a run resumes from a ``TokenBatchProducer`` or
 ``ZeroCopyTokenLoader`` checkpoint and back, at any world size. With ``device="cpu"`` the same planning runs
 with the host ``gather_ragged`` and the host collate.
+
+``plan="device"`` (in-order packing only) moves that host work to the device: the corpus offsets are uploaded
+next to the replica, and per step the host computes the batch's base position in the epoch order, fetches the
+epoch's Feistel round keys and issues launches -- ``token_batch_descriptor`` (index, lengths, running offsets,
+each segment's corpus element), ``pack_plan_device`` and ``pad_pack_tokens_indexed`` reading the plan's counts
+from device memory. No NumPy, no pinned slot, no H2D copy, no host read of anything the device wrote; the shapes
+are therefore static and the counts of a batch are 0-d device tensors (``docs/ARCHITECTURE.md``).
 """
 
 from __future__ import annotations
@@ -36,14 +43,17 @@ from . import _native
 from .exceptions import DDLError
 from .models.tokens import (META_FIELDS, SharedTokenSource, TokenWindowLayout, collate_token_window,
                             drop_cached_views, ffd_order, in_order_rows)
-from .ops.kernels import carve_token_outputs, segment_sources, token_output_bytes
+from .ops.kernels import (carve_token_outputs, device_batch_bytes, device_plan_bytes, launch_device_plan,
+                          pack_tokens_indexed_device, pad_tokens_indexed_device, segment_sources,
+                          token_output_bytes)
 from .permutation import EpochOrder
 from .resident import PrefetchedIndexedLoader
 from .types import DDLEnv
 from .utils import streams
 from .zerocopy import register_mapping, unregister_mapping
 
-_REPLICAS: dict[tuple, list] = {}  # (corpus address, bytes, device index) -> [HBM tensor, users, load seconds]
+# (corpus address, bytes, device index) -> [HBM tensor, users, load seconds, corpus offsets in HBM | None]
+_REPLICAS: dict[tuple, list] = {}
 
 
 def _acquire_replica(source: SharedTokenSource, nbytes: int, device: torch.device, stream, hbm_fraction: float,
@@ -74,8 +84,19 @@ def _acquire_replica(source: SharedTokenSource, nbytes: int, device: torch.devic
             stream.synchronize()
         finally:
             unregister_mapping(base, device, shared=True)
-    _REPLICAS[key] = [hbm, 1, time.perf_counter() - t0]
+    _REPLICAS[key] = [hbm, 1, time.perf_counter() - t0, None]
     return key, hbm, False
+
+
+def _replica_offsets(key: tuple, offsets: torch.Tensor, device: torch.device, stream) -> torch.Tensor:
+    """The corpus offsets (int64 [n + 1]) in HBM, for plans built on the device: uploaded once per replica by the
+    first loader that asks, shared and freed with it."""
+    rep = _REPLICAS[key]
+    if rep[3] is None:
+        with streams.on_stream(stream):
+            rep[3] = offsets.to(device)
+        stream.synchronize()  # bring-up: later loaders over this replica use it from their own streams
+    return rep[3]
 
 
 def _release_replica(key: tuple) -> None:
@@ -90,10 +111,12 @@ def _release_replica(key: tuple) -> None:
 class ResidentTokenLoader(PrefetchedIndexedLoader):
     def __init__(self, source: SharedTokenSource, global_batch: int, seq_len: int = 4096, mode: str = "pad",
                  env: DDLEnv | None = None, *, seed: int = 0, pack_order: str = "in_order",
-                 token_rows: str = "exact", pad_id: int = 0, depth: int = 2,
+                 token_rows: str | None = None, pad_id: int = 0, depth: int = 2,
                  device: str | torch.device | None = None, n_epochs: int | None = None,
                  resume_state: dict | None = None, handoff: str = "device", hbm_fraction: float = 0.8,
-                 chunk_bytes: int = 256 << 20):
+                 chunk_bytes: int = 256 << 20, plan: str = "host"):
+        if plan not in ("host", "device"):
+            raise ValueError("plan must be 'host' or 'device'")
         if handoff not in ("host", "device"):
             raise ValueError("handoff must be 'host' or 'device'")
         if mode not in ("pad", "pack"):
@@ -103,8 +126,18 @@ class ResidentTokenLoader(PrefetchedIndexedLoader):
         if pack_order != "in_order" and mode != "pack":
             raise ValueError(f"pack_order={pack_order!r} reorders rows of a PACKED batch; mode={mode!r} has "
                              "one sequence per row")
+        if token_rows is None:  # unset: the host plan sizes every batch exactly, the device plan cannot
+            token_rows = "fixed" if plan == "device" and mode == "pack" else "exact"
         if token_rows not in ("exact", "fixed"):
             raise ValueError("token_rows must be 'exact' or 'fixed'")
+        if plan == "device":
+            if pack_order == "ffd":
+                raise ValueError("pack_order='ffd' is a sequential bin packing that plan='device' does not build: "
+                                 "use plan='host' (the host plan) for first-fit-decreasing rows")
+            if mode == "pack" and token_rows != "fixed":
+                raise ValueError("plan='device' packs into static shapes (the host never learns the row count): "
+                                 "token_rows must be 'fixed'; token_rows='exact' needs plan='host'")
+        self.plan = plan
         self.handoff = handoff  # batches take microseconds, not a PCIe transfer: the caller's stream waits
         self.env = env or DDLEnv()
         self.W, self.rank = self.env.world_size, self.env.rank
@@ -125,6 +158,9 @@ class ResidentTokenLoader(PrefetchedIndexedLoader):
         self._hdr_bytes = self._reg["tokens"][0]  # meta + header arrays: everything in front of the tokens
         # in front of the header: the kernel's descriptor, src_start [LB] i64 + seg_src [max_segments] i64
         self._desc_bytes = -(-8 * (self.LB + lay.max_segments) // 16) * 16
+        if plan == "device" and self.LB * source.max_len > 0x7FFFFFFF:  # the host plan checks every batch instead
+            raise ValueError(f"{self.LB} sequences of up to {source.max_len} tokens in one batch can overflow int32 "
+                             "cu_seqlens")
         self._toks = source.tokens.tensor().view(-1)  # keeps the mappings alive
         self._offs_t = source.offsets.tensor().view(-1)
         self._offs = self._offs_t.numpy()
@@ -144,6 +180,10 @@ class ResidentTokenLoader(PrefetchedIndexedLoader):
             self._replica_key, self._hbm, self.replica_shared = _acquire_replica(
                 source, self.nbytes, self.device, self.prep_stream, float(hbm_fraction), chunk_bytes)
             self.load_s = _REPLICAS[self._replica_key][2]
+        if plan == "device":
+            self._init_device_plan(gpu)
+            return
+        if gpu:
             win_bytes = self._desc_bytes + self._hdr_bytes  # descriptor + header only: no token ever lands here
             self._windows = [torch.empty(win_bytes, dtype=torch.uint8, device=self.device)
                              for _ in range(self.depth + 1)]
@@ -156,6 +196,77 @@ class ResidentTokenLoader(PrefetchedIndexedLoader):
                              for _ in range(self.depth + 1)]
             self._slots = self._windows  # the CPU twin writes the header straight into the window
         self._views = [self._host_views(b) for b in self._slots]
+
+    def _init_device_plan(self, gpu: bool) -> None:
+        """plan="device": the corpus offsets in HBM, a ring of plan windows (the arrays between the launches;
+        nothing a caller holds) and the per-epoch selectors. The CPU twin needs none of it."""
+        lay, pack = self.layout, self.mode == "pack"
+        self._selectors: dict = {}
+        self._max_seqlen = min(self.seq_len, self.source.max_len)
+        if not gpu:
+            return
+        self._offs_dev = _replica_offsets(self._replica_key, self._offs_t, self.device, self.prep_stream)
+        segs = lay.max_segments if pack else None
+        self._plan_bytes = device_plan_bytes(self.LB, segs, lay.max_segments if pack else 0)
+        self._batch_bytes = device_batch_bytes(lay.max_segments if pack else self.LB, self.seq_len, segs)
+        self._windows = [torch.empty(self._plan_bytes, dtype=torch.uint8, device=self.device)
+                         for _ in range(self.depth + 1)]
+
+    def _selector(self, epoch: int) -> dict:
+        """The ``RowIndex`` arguments of epoch ``epoch``'s order (its Feistel round keys), minus the base."""
+        sel = self._selectors.get(epoch)
+        if sel is None:
+            if len(self._selectors) > 8:
+                self._selectors.clear()
+            perm = self.order.perm(epoch)
+            sel = dict(mode=2, idx=0, **perm.device_args()) if self.order.shuffle else dict(
+                mode=0, idx=0, keys=[0] * 6, n_domain=1, half_bits=1)
+            self._selectors[epoch] = sel
+        return sel
+
+    def _assemble_device_plan(self, t: int):
+        t_host = time.perf_counter()
+        e, g = divmod(t, self.order.batches_per_epoch)
+        base = g * self.GB + self.rank * self.LB
+        lay, S, LB, pack = self.layout, self.seq_len, self.LB, self.mode == "pack"
+        st = self.prep_stream
+        if st is None:  # the CPU twin: the op's reference path
+            perm = self.order.perm(e) if self.order.shuffle else None
+            kw = dict(perm=perm, base=base, count=LB, seq_len=S, pad_id=self.pad_id)
+            if pack:
+                r = pack_tokens_indexed_device(self._toks, self._offs_t, max_rows=lay.max_segments,
+                                               max_segs=lay.max_segments, **kw)
+            else:
+                r = pad_tokens_indexed_device(self._toks, self._offs_t, **kw)
+            ev = None
+        else:
+            timed = self.profile_every > 0 and t % self.profile_every == 0
+            win = self._windows[t % len(self._windows)]
+            with streams.on_stream(st):
+                # one allocation for everything the caller may hold (outputs, cu_seqlens, counts): a held batch
+                # survives the ring of plan windows
+                whole = torch.empty(self._batch_bytes, dtype=torch.uint8, device=self.device)
+                if timed:
+                    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    ev0.record(st)
+                r = launch_device_plan(
+                    win.data_ptr(), whole, corpus_ptr=self._hbm.data_ptr(), corpus_elems=self.n_elems,
+                    tok16=self.source.token_bytes == 2, corpus_offsets_ptr=self._offs_dev.data_ptr(),
+                    n_corpus=self.source.n, selector=dict(self._selector(e), base=base), n=LB, seq_len=S,
+                    pad_id=self.pad_id, pack=pack, max_segs=lay.max_segments if pack else 0,
+                    max_rows=lay.max_segments if pack else 0, stream=st.cuda_stream)
+                if timed:
+                    ev1.record(st)
+                    self._kernel_evs.append((ev0, ev1))
+                ev = torch.cuda.Event()
+                ev.record(st)
+        counts = r.pop("counts")
+        r["n_tokens"] = counts[2]
+        if pack:
+            r["max_seqlen"] = self._max_seqlen  # a static upper bound (varlen attention accepts one)
+            r["n_rows"], r["n_seg"] = counts[0], counts[1]
+        self.assemble_s += time.perf_counter() - t_host
+        return r, ev
 
     @property
     def replica_ptr(self) -> int | None:
@@ -175,6 +286,8 @@ class ResidentTokenLoader(PrefetchedIndexedLoader):
         return v
 
     def _assemble(self, t: int):
+        if self.plan == "device":
+            return self._assemble_device_plan(t)
         t_host = time.perf_counter()
         e, g = divmod(t, self.order.batches_per_epoch)
         lay, S, LB, tb = self.layout, self.seq_len, self.LB, self.source.token_bytes
@@ -276,9 +389,12 @@ class ResidentTokenLoader(PrefetchedIndexedLoader):
         return out
 
     def stats(self) -> dict:
-        return {"batches": self.batches, "source_bytes": self.nbytes, "load_s": self.load_s,
-                "load_gbps": self.nbytes / self.load_s / 1e9 if self.load_s > 0 else 0.0,
-                "handoff": self.handoff, "host_waits": self.host_waits, "replica_shared": self.replica_shared}
+        out = {"batches": self.batches, "source_bytes": self.nbytes, "load_s": self.load_s,
+               "load_gbps": self.nbytes / self.load_s / 1e9 if self.load_s > 0 else 0.0,
+               "handoff": self.handoff, "host_waits": self.host_waits, "replica_shared": self.replica_shared}
+        if self.plan != "host":  # the default mode's stats stay exactly as they were
+            out["plan"] = self.plan
+        return out
 
     def close(self) -> None:
         if self.prep_stream is not None:
@@ -286,12 +402,13 @@ class ResidentTokenLoader(PrefetchedIndexedLoader):
         self._queue.clear()
         self._kernel_evs = []
         if self._windows:
-            if self.prep_stream is None:
+            if self.prep_stream is None and self.plan == "host":
                 drop_cached_views(w.data_ptr() + self._desc_bytes for w in self._windows)
             self._windows = []
         if self._replica_key is not None:
             key, self._replica_key = self._replica_key, None
             self._hbm = None
+            self._offs_dev = None
             _release_replica(key)
 
     def __del__(self):  # pragma: no cover - best effort

@@ -28,6 +28,10 @@ DRAM once). Same batches, same checkpoint.
 must fit: 2-4 bytes per token) and one gfx950 kernel packs every batch straight out of it. Same batches, same
 checkpoint. ``DDL_DEVICE=cpu`` runs it (and ``--zero-copy``) with the host twin.
 
+``--resident --device-plan`` also builds each batch's order and pack plan on the GPU (``plan="device"``): the host
+only issues launches. Packing is in-order, shapes are static (fixed rows, ``cu_seqlens`` of fixed capacity) and
+``n_tokens`` / ``n_rows`` / ``n_seg`` are 0-d device tensors; ``max_seqlen`` is an upper bound.
+
 ``state_dict()`` is the indexed-kind cursor (seed, epoch, global batch), so a
 job can resume at another world size.
 """
@@ -53,9 +57,14 @@ def main() -> None:
                     help="no producers: the GPU gathers the batches out of the registered corpus")
     ap.add_argument("--resident", action="store_true",
                     help="no producers, no PCIe per step: the corpus lives in HBM and one kernel packs the batches")
+    ap.add_argument("--device-plan", action="store_true",
+                    help="with --resident: the batch's order and pack plan are built on the GPU too (in-order "
+                         "packing, static shapes, counts as device scalars)")
     a = ap.parse_args()
     if a.zero_copy and a.resident:
         ap.error("--zero-copy and --resident are two loaders: pick one")
+    if a.device_plan and not a.resident:
+        ap.error("--device-plan is a mode of --resident")
 
     name = f"ddl_amd_example_tok_{os.environ.get('MASTER_PORT', os.getpid())}"
     creator = int(os.environ.get("LOCAL_RANK", "0")) == 0
@@ -71,7 +80,10 @@ def main() -> None:
                 n_tok = int(offs.tensor()[-1])
                 src = SharedTokenSource(SharedArraySource(name + "_tok", n_tok, (1,), "int32"), offs, a.seq_len)
             pack_order = "ffd" if a.mode == "pack" else "in_order"
-            if a.resident:
+            if a.resident and a.device_plan:  # first-fit-decreasing is a host plan
+                dl = ddl_amd.ResidentTokenLoader(src, a.global_batch, a.seq_len, a.mode, env, n_epochs=a.epochs,
+                                                 plan="device")
+            elif a.resident:
                 dl = ddl_amd.ResidentTokenLoader(src, a.global_batch, a.seq_len, a.mode, env, pack_order=pack_order,
                                                  n_epochs=a.epochs)
             elif a.zero_copy:
@@ -87,12 +99,13 @@ def main() -> None:
                 real = rows = 0
                 for b in dl:
                     real += int(b["attention_mask"].sum())
-                    rows += b["input_ids"].shape[0]
+                    rows += int(b.get("n_rows", b["input_ids"].shape[0]))  # fixed rows: the packed ones
                 if env.rank == 0:
                     # cu_seqlens has one entry per SEGMENT: over-long sequences are split into seq_len chunks
                     # and empty sequences have none, so this is not the sequence count
-                    extra = (f", {b['cu_seqlens'].numel() - 1} segments (max {b['max_seqlen']} tokens) in the "
-                             "last batch" if a.mode == "pack" else "")
+                    n_seg = int(b["n_seg"]) if "n_seg" in b else b["cu_seqlens"].numel() - 1 if a.mode == "pack" else 0
+                    extra = (f", {n_seg} segments (max {b['max_seqlen']} tokens) in the last batch"
+                             if a.mode == "pack" else "")
                     print(f"epoch {epoch}: {rows} rows x {a.seq_len} on rank 0, {real} real tokens "
                           f"({100.0 * real / max(rows * a.seq_len, 1):.1f}% dense){extra}; keys {sorted(b)}",
                           flush=True)
