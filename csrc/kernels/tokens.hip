@@ -10,59 +10,39 @@
 // position id restarts at every sequence boundary and a segment id marks
 // which sequence a token belongs to (what varlen attention consumes).
 //
-// Grid: one workgroup per (row, chunk of kSpan positions), so a 64 x 4096
-// batch is 512 workgroups (the first form ran one workgroup per row: 64 of the
-// 256 CUs busy). Each lane writes 4 consecutive positions as 16 B (tokens,
-// i32 ids) / 4 B (mask) vectors. Pack mode copies the sequence starts into
-// LDS once per workgroup (one coalesced read) and binary-searches there; the
-// first form binary-searched global memory for every token, a chain of
-// ~log2(n_seg) dependent loads per position.
+// The grid, the prologue and the stores are tokens_emit.h / tokens_indexed.h, shared with the indexed kernel
+// (tokens_indexed.hip). This file's part is the lane loop: a token is a plain load of tokens[start + p], whose
+// address does not wait for the segment search -- no bounds check (the plan is the caller's and indexes its
+// own stream), one LDS array (the segment starts; there is no second descriptor to stage). The indexed
+// kernel's ti_lane4, which derives the element from the searched segment, made pack mode 18% slower here
+// (profiles/token_refactor), so the two lane loops stay apart.
 #include "common.h"
 #include "launch.h"
+#include "tokens_emit.h"
 
 namespace ddl {
 namespace {
 
-constexpr int kThreads = 128;
-constexpr int kSpan = kThreads * 4;  // positions per workgroup
-constexpr int kSegCap = 1024;        // sequence starts staged in LDS (8 KB)
-
-// index of the last entry <= v of the sorted a[0..n) (a[0] <= v)
 template <typename At>
-__device__ __forceinline__ int64_t last_le(At at, int64_t n, int64_t v) {
-  int64_t lo = 0, hi = n;
-  while (lo < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (at(mid) <= v)
-      lo = mid + 1;
-    else
-      hi = mid;
-  }
-  return lo - 1;
-}
-
-template <typename At>
-__device__ __forceinline__ void emit4(const TokenSpec& sp, int64_t row, int64_t p0, int64_t start, int64_t len,
-                                      At seg_at) {
-  const int64_t S = sp.seq_len;
-  const int32_t* src = static_cast<const int32_t*>(sp.tokens) + start;
-  const uint16_t* src16 = static_cast<const uint16_t*>(sp.tokens) + start;
-  int32_t tok[4], pos[4], seg[4];
-  uint8_t msk[4];
+__device__ __forceinline__ void emit4(const TokenSpec& sp, const TiRow& r, At seg_at) {
+  const int32_t* src = static_cast<const int32_t*>(sp.tokens) + r.start;
+  const uint16_t* src16 = static_cast<const uint16_t*>(sp.tokens) + r.start;
+  int32_t tok[kTiLane], pos[kTiLane], seg[kTiLane];
+  uint8_t msk[kTiLane];
   int64_t s = -1;  // current sequence (pack mode): searched once, then advanced
 #pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const int64_t p = p0 + k;
-    const bool valid = p < len;
+  for (int k = 0; k < kTiLane; ++k) {
+    const int64_t p = r.p0 + k;
+    const bool valid = p < r.len;
     tok[k] = valid ? (sp.tok16 ? static_cast<int32_t>(src16[p]) : src[p]) : sp.pad_id;
     msk[k] = valid ? 1 : 0;
     if (sp.mode == 0) {
       pos[k] = valid ? static_cast<int32_t>(p) : 0;
       seg[k] = 0;
     } else if (valid) {
-      const int64_t g = start + p;  // flat token index
+      const int64_t g = r.start + p;  // flat token index
       if (s < 0)
-        s = last_le(seg_at, sp.n_seg + 1, g);
+        s = ti_last_le(seg_at, sp.n_seg + 1, g);
       else
         while (s + 1 <= sp.n_seg && seg_at(s + 1) <= g) ++s;
       pos[k] = static_cast<int32_t>(g - seg_at(s));
@@ -72,78 +52,21 @@ __device__ __forceinline__ void emit4(const TokenSpec& sp, int64_t row, int64_t 
       seg[k] = -1;
     }
   }
-  const int64_t o = row * S + p0;
-  if (p0 + 4 <= S && (S % 4 == 0)) {
-    *reinterpret_cast<int4*>(sp.out_tokens + o) = make_int4(tok[0], tok[1], tok[2], tok[3]);
-    if (sp.attn_mask) {
-      const uint32_t m = msk[0] | (msk[1] << 8) | (msk[2] << 16) | (static_cast<uint32_t>(msk[3]) << 24);
-      *reinterpret_cast<uint32_t*>(sp.attn_mask + o) = m;
-    }
-    if (sp.position_ids) {
-      if (sp.pos_is_i64) {
-        int64_t* pp = static_cast<int64_t*>(sp.position_ids) + o;
-        *reinterpret_cast<longlong2*>(pp) = make_longlong2(pos[0], pos[1]);
-        *reinterpret_cast<longlong2*>(pp + 2) = make_longlong2(pos[2], pos[3]);
-      } else {
-        *reinterpret_cast<int4*>(static_cast<int32_t*>(sp.position_ids) + o) = make_int4(pos[0], pos[1], pos[2], pos[3]);
-      }
-    }
-    if (sp.segment_ids) *reinterpret_cast<int4*>(sp.segment_ids + o) = make_int4(seg[0], seg[1], seg[2], seg[3]);
-  } else {
-    for (int k = 0; k < 4 && p0 + k < S; ++k) {
-      sp.out_tokens[o + k] = tok[k];
-      if (sp.attn_mask) sp.attn_mask[o + k] = msk[k];
-      if (sp.position_ids) {
-        if (sp.pos_is_i64)
-          static_cast<int64_t*>(sp.position_ids)[o + k] = pos[k];
-        else
-          static_cast<int32_t*>(sp.position_ids)[o + k] = pos[k];
-      }
-      if (sp.segment_ids) sp.segment_ids[o + k] = seg[k];
-    }
-  }
+  ti_store4(sp, r.row, r.p0, tok, pos, seg, msk);
 }
 
-// One workgroup = (row, chunk) `bx` of batch `sp`. Blocks past the batch's rows (a multi-batch launch is
-// sized for its largest sub-batch) only do block 0's cu_seqlens copy; the exit is block-uniform.
 __device__ __forceinline__ void pad_pack_block(const TokenSpec& spec, uint32_t bx, int32_t chunks, int64_t* seg_lds) {
   TokenSpec sp = spec;
-  if (sp.dev_counts != nullptr) {  // plan built on the device: its row / segment counts (block-uniform loads)
-    sp.rows = sp.dev_counts[0] < 0 ? 0 : sp.dev_counts[0];
-    sp.n_seg = sp.dev_counts[0] < 0 ? 0 : sp.dev_counts[1];
-  }
-  const uint32_t row = bx / static_cast<uint32_t>(chunks);
-  const bool live = row < (sp.fill_rows > sp.rows ? sp.fill_rows : sp.rows);  // data row or padding row
-  const int64_t p0 = static_cast<int64_t>(bx - row * static_cast<uint32_t>(chunks)) * kSpan +
-                     static_cast<int64_t>(threadIdx.x) * 4;
-  int64_t start = 0, len = 0;  // a padding row: len 0, every position written as padding
-  if (row < sp.rows) {
-    if (sp.mode == 0) {
-      start = sp.offsets[row];
-      len = sp.offsets[row + 1] - start;
-    } else {
-      start = sp.row_start[row];
-      len = sp.row_end[row] - start;
-    }
-  }
-  if (len > sp.seq_len) len = sp.seq_len;
-  if (len < 0) len = 0;
-  const bool staged = sp.mode == 1 && sp.n_seg + 1 <= kSegCap;  // batch-uniform
-  if (staged && live)
-    for (int64_t i = threadIdx.x; i <= sp.n_seg; i += kThreads) seg_lds[i] = sp.seg_offsets[i];
-  if (sp.cu_seqlens_out != nullptr && bx == 0)  // owned copy of the sequence starts (cu_seqlens)
-    for (int64_t i = threadIdx.x; i <= sp.n_seg; i += kThreads)
-      sp.cu_seqlens_out[i] = static_cast<int32_t>(sp.seg_offsets[i]);
-  __syncthreads();
-  if (!live || p0 >= sp.seq_len) return;
-  if (staged)
-    emit4(sp, row, p0, start, len, [&](int64_t i) { return seg_lds[i]; });
+  const TiRow r = ti_prologue(sp, bx, chunks, seg_lds, 0, [](int64_t) {});
+  if (!r.live || r.p0 >= sp.seq_len) return;
+  if (r.staged)
+    emit4(sp, r, [&](int64_t i) { return seg_lds[i]; });
   else
-    emit4(sp, row, p0, start, len, [&](int64_t i) { return sp.seg_offsets[i]; });
+    emit4(sp, r, [&](int64_t i) { return sp.seg_offsets[i]; });
 }
 
-__global__ void __launch_bounds__(kThreads) pad_pack_kernel(TokenSpec sp, int32_t chunks) {
-  __shared__ int64_t seg_lds[kSegCap];
+__global__ void __launch_bounds__(kTiThreads) pad_pack_kernel(TokenSpec sp, int32_t chunks) {
+  __shared__ int64_t seg_lds[kTiSegCap];
   pad_pack_block(sp, blockIdx.x, chunks, seg_lds);
 }
 
@@ -151,8 +74,8 @@ struct TokenMulti {
   TokenSpec sub[kMaxTokenSubs];
 };
 
-__global__ void __launch_bounds__(kThreads) pad_pack_multi_kernel(TokenMulti m, int32_t chunks) {
-  __shared__ int64_t seg_lds[kSegCap];
+__global__ void __launch_bounds__(kTiThreads) pad_pack_multi_kernel(TokenMulti m, int32_t chunks) {
+  __shared__ int64_t seg_lds[kTiSegCap];
   pad_pack_block(m.sub[blockIdx.y], blockIdx.x, chunks, seg_lds);
 }
 
@@ -284,14 +207,13 @@ int pack_plan_device(const PackPlanSpec& spec, hipStream_t st) {
 }
 
 int pad_pack_tokens(const TokenSpec& spec, hipStream_t st) {
-  const int64_t rows = spec.fill_rows > spec.rows ? spec.fill_rows : spec.rows;
-  if (rows <= 0 || spec.seq_len <= 0) return 0;
+  const int64_t grid = spec.seq_len > 0 ? ti_grid(spec.rows, spec.fill_rows, spec.seq_len, false) : 0;
+  if (grid == 0) return 0;
   if (spec.mode == 0 && !spec.offsets) return -2;
   if (spec.mode == 1 && (!spec.row_start || !spec.row_end || !spec.seg_offsets)) return -2;
-  const int64_t chunks = (spec.seq_len + kSpan - 1) / kSpan;
-  if (rows * chunks >= (int64_t{1} << 31)) return -4;
-  hipLaunchKernelGGL(pad_pack_kernel, dim3(static_cast<uint32_t>(rows * chunks)), dim3(kThreads), 0, st, spec,
-                     static_cast<int32_t>(chunks));
+  if (grid < 0) return -4;
+  hipLaunchKernelGGL(pad_pack_kernel, dim3(static_cast<uint32_t>(grid)), dim3(kTiThreads), 0, st, spec,
+                     static_cast<int32_t>(ti_chunks(spec.seq_len)));
   return static_cast<int>(hipGetLastError());
 }
 
@@ -311,10 +233,10 @@ int pad_pack_tokens_multi(const TokenSpec* specs, int n, hipStream_t st) {
       if (sp.fill_rows > max_rows) max_rows = sp.fill_rows;
       m.sub[j] = sp;
     }
-    const int64_t chunks = (seq_len + kSpan - 1) / kSpan;
-    if (max_rows * chunks >= (int64_t{1} << 31)) return -4;
-    hipLaunchKernelGGL(pad_pack_multi_kernel, dim3(static_cast<uint32_t>(max_rows * chunks), static_cast<uint32_t>(cnt)),
-                       dim3(kThreads), 0, st, m, static_cast<int32_t>(chunks));
+    const int64_t grid = ti_grid(max_rows, 0, seq_len, false);
+    if (grid < 0) return -4;
+    hipLaunchKernelGGL(pad_pack_multi_kernel, dim3(static_cast<uint32_t>(grid), static_cast<uint32_t>(cnt)),
+                       dim3(kTiThreads), 0, st, m, static_cast<int32_t>(ti_chunks(seq_len)));
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return static_cast<int>(e);
   }

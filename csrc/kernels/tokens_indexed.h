@@ -1,8 +1,10 @@
-// Index arithmetic of the indexed pad/pack kernel (tokens_indexed.hip), shared with host code:
-// csrc/kernels/tests/tokens_indexed_check.cpp replays the kernel's per-lane loops with it under ASan/UBSan.
+// Index arithmetic of the pad/pack kernels, shared with host code. The constants, the grid, the lane origin, the
+// row length, the vector-store predicate and the search serve the flat kernel (tokens.hip) and the indexed one
+// (tokens_indexed.hip) alike (their shared device half is tokens_emit.h); ti_lane4 is the indexed kernel's lane
+// loop, which csrc/kernels/tests/tokens_indexed_check.cpp replays under ASan/UBSan.
 // Plain inline functions: __host__ __device__ under hipcc, plain under g++ (this header includes nothing of HIP).
 //
-// The kernel writes what pad_pack_tokens (tokens.hip) writes for the VIRTUAL flat stream
+// The indexed kernel writes what pad_pack_tokens (tokens.hip) writes for the VIRTUAL flat stream
 //   concat(corpus[src_start[i] : src_start[i] + len_i]),   len_i = offsets[i + 1] - offsets[i],
 // which never exists: a token is read from the corpus at
 //   pad mode   corpus[src_start[row] + p]                     p < min(len_row, S)
@@ -31,7 +33,9 @@ constexpr int kTiSegCap = 1024;             // segment starts (and their corpus 
 DDL_TI_HD int64_t ti_chunks(int64_t seq_len) { return (seq_len + kTiSpan - 1) / kTiSpan; }
 
 // workgroups of a launch: one per (row, chunk), at least one when block 0 has cu_seqlens to write; -1: the
-// grid does not fit 31 bits
+// grid does not fit 31 bits. The test is rows >= 2^31 / chunks: where chunks does not divide 2^31 it also refuses
+// the last fewer-than-chunks grids below 2^31, which pad_pack_tokens' former rows * chunks >= 2^31 let through
+// (about 2^31 workgroups: 18 TB of outputs, beyond any device)
 DDL_TI_HD int64_t ti_grid(int64_t rows, int64_t fill_rows, int64_t seq_len, bool has_cu) {
   const int64_t r = fill_rows > rows ? fill_rows : rows;
   const int64_t chunks = ti_chunks(seq_len);

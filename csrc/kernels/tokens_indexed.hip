@@ -4,13 +4,12 @@
 // flat window followed by pad_pack_tokens out of it is two launches and one extra HBM write and read of every
 // token; here every token is read once, from the corpus, by the lane that writes it.
 //
-// Shape: pad_pack_kernel's. One workgroup per (row, chunk of kTiSpan = 512 positions), 4 positions per lane,
-// 16-byte stores of ids / i32 position ids / segment ids (2 x 16 B for i64 position ids) and a 4-byte mask
-// store, per-element stores where the row width is no multiple of 4. Pack mode stages seg_offsets and seg_src
-// in LDS (2 x 8 KB) when n_seg + 1 <= kTiSegCap and binary-searches global memory otherwise; a lane searches
-// once and then advances. The kernel is write-bound (~17 B stored per token against 2-4 B read), so the source
-// side stays simple: one element load per token at element alignment, non-temporal (the corpus streams
-// through; the fresh batch is what should stay in the cache). All the index arithmetic is tokens_indexed.h.
+// The grid, the prologue and the stores are tokens_emit.h / tokens_indexed.h, shared with pad_pack_kernel. This
+// file's part: the lane loop (ti_lane4: the element follows from the searched segment), seg_src staged next to
+// seg_offsets in pack mode (a second 8 KB LDS array), the tail of a fixed-capacity cu_seqlens, and the load.
+// The kernel is write-bound (~17 B stored per token against 2-4 B read), so the source side stays simple: one
+// element load per token at element alignment, bounds-checked, non-temporal (the corpus streams through; the
+// fresh batch is what should stay in the cache).
 //
 // Bounded reads: a corpus element is read only for a position p < min(len, S) of a data row, at
 //   pad   src_start[row] + p,                    p < len_row
@@ -23,12 +22,12 @@
 // are inside the row), so every element of every [R, S] output is written once and nothing outside;
 // cu_seqlens_out[0 .. n_seg] is written by block 0, and with a capacity (cu_cap) also (n_seg, cu_cap].
 // A plan built on the device (dev_counts, pack mode): rows and n_seg are two block-uniform loads of the plan's
-// counts, clamped as pad_pack_block (tokens.hip) clamps them -- a negative row count, an overflowed plan, makes
-// every row padding; the grid covers fill_rows, the plan's row capacity, and pack_plan_device never reports
+// counts, clamped by ti_prologue (tokens_emit.h) -- a negative row count, an overflowed plan, makes every row
+// padding; the grid covers fill_rows, the plan's row capacity, and pack_plan_device never reports
 // more rows or segments than its capacities, which are the sizes of row_start / row_end / seg_offsets / seg_src.
 #include "common.h"
 #include "launch.h"
-#include "tokens_indexed.h"
+#include "tokens_emit.h"
 
 namespace ddl {
 namespace {
@@ -42,15 +41,28 @@ struct IndexedSpec {
   int64_t cu_cap;            // > 0: cu_seqlens_out holds cu_cap + 1 entries, those past n_seg = the token count
 };
 
-template <typename SegAt, typename SrcAt>
-__device__ __forceinline__ void emit4_indexed(const IndexedSpec& ix, int64_t row, int64_t p0, int64_t start,
-                                              int64_t len, int64_t src0, SegAt seg_at, SrcAt src_at) {
-  const TokenSpec& sp = ix.tok;
-  const int64_t S = sp.seq_len;
-  TiLane4 ln;
-  ti_lane4(sp.mode, p0, start, len, src0, sp.n_seg, seg_at, src_at, &ln);
+__global__ void __launch_bounds__(kTiThreads) pad_pack_indexed_kernel(IndexedSpec ix, int32_t chunks) {
+  __shared__ int64_t seg_lds[kTiSegCap];
+  __shared__ int64_t src_lds[kTiSegCap];
+  TokenSpec& sp = ix.tok;
+  const TiRow r =
+      ti_prologue(sp, blockIdx.x, chunks, seg_lds, ix.cu_cap, [&](int64_t i) { src_lds[i] = ix.seg_src[i]; });
+  if (sp.cu_seqlens_out != nullptr && blockIdx.x == 0 && ix.cu_cap > r.n_cu) {
+    // the tail of a fixed-capacity cu_seqlens, behind the prologue's copy: zero-length sequences at the token count
+    const int32_t total = static_cast<int32_t>(sp.seg_offsets[r.n_cu]);
+    for (int64_t i = r.n_cu + 1 + threadIdx.x; i <= ix.cu_cap; i += kTiThreads) sp.cu_seqlens_out[i] = total;
+  }
+  if (!r.live || r.p0 >= sp.seq_len) return;
+  const int64_t src0 = sp.mode == 0 && r.row < sp.rows ? ix.src_start[r.row] : 0;
   const int32_t* c32 = static_cast<const int32_t*>(ix.corpus);
   const uint16_t* c16 = static_cast<const uint16_t*>(ix.corpus);
+  TiLane4 ln;
+  if (r.staged)
+    ti_lane4(sp.mode, r.p0, r.start, r.len, src0, sp.n_seg, [&](int64_t i) { return seg_lds[i]; },
+             [&](int64_t i) { return src_lds[i]; }, &ln);
+  else
+    ti_lane4(sp.mode, r.p0, r.start, r.len, src0, sp.n_seg, [&](int64_t i) { return sp.seg_offsets[i]; },
+             [&](int64_t i) { return ix.seg_src[i]; }, &ln);
   int32_t tok[kTiLane];
 #pragma unroll
   for (int k = 0; k < kTiLane; ++k) {
@@ -58,89 +70,9 @@ __device__ __forceinline__ void emit4_indexed(const IndexedSpec& ix, int64_t row
     if (static_cast<uint64_t>(e) < static_cast<uint64_t>(ix.corpus_elems))  // -1 (padding) fails it too
       tok[k] = sp.tok16 ? static_cast<int32_t>(__builtin_nontemporal_load(c16 + e)) : __builtin_nontemporal_load(c32 + e);
     else
-      tok[k] = sp.pad_id;
+      tok[k] = sp.pad_id;  // a corrupt descriptor's element outside the corpus is not dereferenced
   }
-  const int64_t o = row * S + p0;
-  if (ti_vector_store(p0, S)) {
-    *reinterpret_cast<int4*>(sp.out_tokens + o) = make_int4(tok[0], tok[1], tok[2], tok[3]);
-    if (sp.attn_mask) {
-      const uint32_t m = ln.msk[0] | (ln.msk[1] << 8) | (ln.msk[2] << 16) | (static_cast<uint32_t>(ln.msk[3]) << 24);
-      *reinterpret_cast<uint32_t*>(sp.attn_mask + o) = m;
-    }
-    if (sp.position_ids) {
-      if (sp.pos_is_i64) {
-        int64_t* pp = static_cast<int64_t*>(sp.position_ids) + o;
-        *reinterpret_cast<longlong2*>(pp) = make_longlong2(ln.pos[0], ln.pos[1]);
-        *reinterpret_cast<longlong2*>(pp + 2) = make_longlong2(ln.pos[2], ln.pos[3]);
-      } else {
-        *reinterpret_cast<int4*>(static_cast<int32_t*>(sp.position_ids) + o) =
-            make_int4(ln.pos[0], ln.pos[1], ln.pos[2], ln.pos[3]);
-      }
-    }
-    if (sp.segment_ids)
-      *reinterpret_cast<int4*>(sp.segment_ids + o) = make_int4(ln.seg[0], ln.seg[1], ln.seg[2], ln.seg[3]);
-  } else {
-    for (int k = 0; k < kTiLane && p0 + k < S; ++k) {
-      sp.out_tokens[o + k] = tok[k];
-      if (sp.attn_mask) sp.attn_mask[o + k] = ln.msk[k];
-      if (sp.position_ids) {
-        if (sp.pos_is_i64)
-          static_cast<int64_t*>(sp.position_ids)[o + k] = ln.pos[k];
-        else
-          static_cast<int32_t*>(sp.position_ids)[o + k] = ln.pos[k];
-      }
-      if (sp.segment_ids) sp.segment_ids[o + k] = ln.seg[k];
-    }
-  }
-}
-
-__global__ void __launch_bounds__(kTiThreads) pad_pack_indexed_kernel(IndexedSpec ix, int32_t chunks) {
-  __shared__ int64_t seg_lds[kTiSegCap];
-  __shared__ int64_t src_lds[kTiSegCap];
-  TokenSpec& sp = ix.tok;
-  if (sp.dev_counts != nullptr) {  // plan built on the device: its row / segment counts (block-uniform loads)
-    const int64_t n_rows = sp.dev_counts[0];
-    sp.rows = n_rows < 0 ? 0 : n_rows;
-    sp.n_seg = n_rows < 0 ? 0 : sp.dev_counts[1];
-  }
-  int64_t row, p0;
-  ti_lane_origin(blockIdx.x, chunks, static_cast<int>(threadIdx.x), &row, &p0);
-  const bool live = row < (sp.fill_rows > sp.rows ? sp.fill_rows : sp.rows);  // data row or padding row
-  int64_t start = 0, len = 0, src0 = 0;  // a padding row: len 0, every position written as padding
-  if (row < sp.rows) {
-    if (sp.mode == 0) {
-      start = sp.offsets[row];
-      len = sp.offsets[row + 1] - start;
-      src0 = ix.src_start[row];
-    } else {
-      start = sp.row_start[row];
-      len = sp.row_end[row] - start;
-    }
-  }
-  len = ti_row_len(len, sp.seq_len);
-  const bool staged = sp.mode == 1 && sp.n_seg + 1 <= kTiSegCap;  // batch-uniform
-  if (staged && live)
-    for (int64_t i = threadIdx.x; i <= sp.n_seg; i += kTiThreads) {
-      seg_lds[i] = sp.seg_offsets[i];
-      if (i < sp.n_seg) src_lds[i] = ix.seg_src[i];
-    }
-  if (sp.cu_seqlens_out != nullptr && blockIdx.x == 0) {  // owned copy of the sequence starts (cu_seqlens)
-    const int64_t n_cu = ti_cu_entries(sp.n_seg, ix.cu_cap);
-    for (int64_t i = threadIdx.x; i <= n_cu; i += kTiThreads)
-      sp.cu_seqlens_out[i] = static_cast<int32_t>(sp.seg_offsets[i]);
-    if (ix.cu_cap > n_cu) {  // the tail of a fixed-capacity cu_seqlens: zero-length sequences at the token count
-      const int32_t total = static_cast<int32_t>(sp.seg_offsets[n_cu]);
-      for (int64_t i = n_cu + 1 + threadIdx.x; i <= ix.cu_cap; i += kTiThreads) sp.cu_seqlens_out[i] = total;
-    }
-  }
-  __syncthreads();
-  if (!live || p0 >= sp.seq_len) return;
-  if (staged)
-    emit4_indexed(ix, row, p0, start, len, src0, [&](int64_t i) { return seg_lds[i]; },
-                  [&](int64_t i) { return src_lds[i]; });
-  else
-    emit4_indexed(ix, row, p0, start, len, src0, [&](int64_t i) { return sp.seg_offsets[i]; },
-                  [&](int64_t i) { return ix.seg_src[i]; });
+  ti_store4(sp, r.row, r.p0, tok, ln.pos, ln.seg, ln.msk);
 }
 
 }  // namespace

@@ -184,6 +184,28 @@ def in_order_rows(lengths: np.ndarray, seq_len: int) -> int:
     return int(_native.runtime().in_order_rows(np.ascontiguousarray(lengths, dtype=np.int64), int(seq_len)))
 
 
+def ffd_if_it_wins(lengths: np.ndarray, seq_len: int) -> np.ndarray | None:
+    """The ``pack_order="ffd"`` rule of every token path: the first-fit-decreasing order of one batch's sequences
+    if it packs them into fewer rows than their given order does, else None (FFD is a heuristic)."""
+    order, ffd_rows = ffd_order(lengths, seq_len)
+    return order if ffd_rows < in_order_rows(lengths, seq_len) else None
+
+
+def check_token_options(mode: str, pack_order: str, token_rows: str = "exact", handoff: str = "host") -> None:
+    """The options every token path takes (the producer has no ``token_rows`` / ``handoff`` of its own)."""
+    if handoff not in ("host", "device"):
+        raise ValueError("handoff must be 'host' or 'device'")
+    if mode not in ("pad", "pack"):
+        raise ValueError("mode must be 'pad' or 'pack'")
+    if pack_order not in ("in_order", "ffd"):
+        raise ValueError("pack_order must be 'in_order' or 'ffd'")
+    if pack_order != "in_order" and mode != "pack":
+        raise ValueError(f"pack_order={pack_order!r} reorders rows of a PACKED batch; mode={mode!r} has "
+                         "one sequence per row")
+    if token_rows not in ("exact", "fixed"):
+        raise ValueError("token_rows must be 'exact' or 'fixed'")
+
+
 def in_order_rows_py(lengths: np.ndarray, seq_len: int) -> int:
     S = int(seq_len)
     rows, cur = 0, S  # cur = tokens in the open row (S: no open row)
@@ -262,13 +284,7 @@ class TokenBatchProducer(ProducerFunctionSkeleton):
         if batches_per_window < 1:
             raise ValueError("batches_per_window must be >= 1")
         self.batches_per_window = int(batches_per_window)
-        if mode not in ("pad", "pack"):
-            raise ValueError("mode must be 'pad' or 'pack'")
-        if pack_order not in ("in_order", "ffd"):
-            raise ValueError("pack_order must be 'in_order' or 'ffd'")
-        if pack_order != "in_order" and mode != "pack":
-            raise ValueError(f"pack_order={pack_order!r} reorders rows of a PACKED batch; mode={mode!r} has "
-                             "one sequence per row")
+        check_token_options(mode, pack_order)
         self.pack_order = pack_order
         self.source, self.global_batch, self.seq_len, self.mode, self.seed = source, global_batch, seq_len, mode, seed
         self.host_threads = host_threads
@@ -333,9 +349,8 @@ class TokenBatchProducer(ProducerFunctionSkeleton):
             epoch, g = divmod(base + j, bpe)
             idx = np.asarray(self.order.indices(epoch, g, rank, world), dtype=np.int64)
             if pack and ffd:
-                lens = offs_all[idx + 1] - offs_all[idx]
-                order, ffd_rows = ffd_order(lens, S)
-                if ffd_rows < in_order_rows(lens, S):  # FFD is a heuristic: keep it only if it wins
+                order = ffd_if_it_wins(offs_all[idx + 1] - offs_all[idx], S)
+                if order is not None:
                     idx = idx[order]
             o_ptr, rs_ptr, re_ptr, so_ptr, so_np = subs[j]
             # native ragged gather (thread pool, GIL released): sequences -> window, offsets alongside
@@ -406,23 +421,11 @@ def collate_token_window(buf: torch.Tensor, layout: TokenWindowLayout, mode: str
                 "n_tokens": n_tokens, **extra}
     dev = tokens.device
     s = layout.seq_len
-    # one allocation for all five outputs (aligned regions: position_ids i64, cu_seqlens i32,
-    # input_ids i32, segment_ids i32, attention_mask u8). cu_seqlens is written by the kernel into
+    # one allocation for all five outputs (ops.carve_token_outputs). cu_seqlens is written by the kernel into
     # memory of its own: a view of the staging buffer would be overwritten when it is re-staged
     R = max(n_rows, fill)
-    n = R * s
-    cu_n = -(-(n_seg + 1) // 4) * 4  # i32 count rounded so the following regions stay 16-byte aligned
-    whole = torch.empty(8 * n + 4 * cu_n + 4 * n + 4 * n + n, dtype=torch.uint8, device=dev)
-    o = 0
-    pos = whole[o:o + 8 * n].view(torch.int64).view(R, s)
-    o += 8 * n
-    cu = whole[o:o + 4 * (n_seg + 1)].view(torch.int32)
-    o += 4 * cu_n
-    ids = whole[o:o + 4 * n].view(torch.int32).view(R, s)
-    o += 4 * n
-    seg = whole[o:o + 4 * n].view(torch.int32).view(R, s)
-    o += 4 * n
-    mask = whole[o:o + n].view(R, s)
+    whole = torch.empty(ops.token_output_bytes(R, s, n_seg), dtype=torch.uint8, device=dev)
+    ids, mask, pos, seg, cu = ops.carve_token_outputs(whole, R, s, n_seg)
     from ..ops.kernels import _stream_handle
 
     if n_tokens > 0x7FFFFFFF:

@@ -829,34 +829,39 @@ def _align16(n: int) -> int:
 def token_output_bytes(rows: int, seq_len: int, n_seg: int | None = None, position_dtype=torch.int64) -> int:
     """Bytes of the one allocation that ``carve_token_outputs`` cuts a [rows, seq_len] token batch from
     (``n_seg`` None: pad mode, no segment ids and no cu_seqlens)."""
+    # per-step host code of every token path: (x + 15) & -16 is _align16(x), written out to spare the calls
     n = int(rows) * int(seq_len)
-    pb = 8 if position_dtype == torch.int64 else 4
-    total = _align16(pb * n) + _align16(4 * n) + _align16(n)
+    pos_b = (8 if position_dtype == torch.int64 else 4) * n
+    ids_b = (4 * n + 15) & -16  # input ids, and the segment ids
+    total = ((pos_b + 15) & -16) + ids_b + ((n + 15) & -16)  # position ids, input ids, mask
     if n_seg is not None:
-        total += _align16(4 * (int(n_seg) + 1)) + _align16(4 * n)
+        total += ((4 * (n_seg + 1) + 15) & -16) + ids_b  # cu_seqlens [n_seg + 1] i32, segment ids
     return total
 
 
 def carve_token_outputs(whole: torch.Tensor, rows: int, seq_len: int, n_seg: int | None = None,
                         position_dtype=torch.int64):
     """(input_ids, attention_mask, position_ids, segment_ids | None, cu_seqlens | None) as views of the uint8
-    buffer ``whole``, in the order ``collate_token_window`` lays them out (position ids, cu_seqlens, input ids,
-    segment ids, mask), every region starting 16-byte aligned."""
+    buffer ``whole``: position ids, cu_seqlens, input ids, segment ids, mask, every region starting 16-byte
+    aligned. The one definition of a token batch's allocation: ``collate_token_window``, the indexed ops and the
+    resident loader all carve with it."""
     R, S = int(rows), int(seq_len)
     n = R * S
-    pb = 8 if position_dtype == torch.int64 else 4
-    o = 0
-    pos = whole[o:o + pb * n].view(position_dtype).view(R, S)
-    o += _align16(pb * n)
+    pos_b = (8 if position_dtype == torch.int64 else 4) * n
+    ids_b = 4 * n
+    ids_a = (ids_b + 15) & -16  # _align16, written out as in token_output_bytes
+    pos = whole[:pos_b].view(position_dtype).view(R, S)
+    o = (pos_b + 15) & -16
     cu = seg = None
     if n_seg is not None:
-        cu = whole[o:o + 4 * (n_seg + 1)].view(torch.int32)
-        o += _align16(4 * (n_seg + 1))
-    ids = whole[o:o + 4 * n].view(torch.int32).view(R, S)
-    o += _align16(4 * n)
+        cu_b = 4 * (n_seg + 1)
+        cu = whole[o:o + cu_b].view(torch.int32)
+        o += (cu_b + 15) & -16
+    ids = whole[o:o + ids_b].view(torch.int32).view(R, S)
+    o += ids_a
     if n_seg is not None:
-        seg = whole[o:o + 4 * n].view(torch.int32).view(R, S)
-        o += _align16(4 * n)
+        seg = whole[o:o + ids_b].view(torch.int32).view(R, S)
+        o += ids_a
     mask = whole[o:o + n].view(R, S)
     return ids, mask, pos, seg, cu
 

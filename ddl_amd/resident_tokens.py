@@ -41,13 +41,11 @@ import torch
 
 from . import _native
 from .exceptions import DDLError
-from .models.tokens import (META_FIELDS, SharedTokenSource, TokenWindowLayout, collate_token_window,
-                            drop_cached_views, ffd_order, in_order_rows)
+from .models.tokens import SharedTokenSource, check_token_options, drop_cached_views
 from .ops.kernels import (carve_token_outputs, device_batch_bytes, device_plan_bytes, launch_device_plan,
                           pack_tokens_indexed_device, pad_tokens_indexed_device, segment_sources,
                           token_output_bytes)
-from .permutation import EpochOrder
-from .resident import PrefetchedIndexedLoader
+from .token_plan import HostPlannedTokenLoader
 from .types import DDLEnv
 from .utils import streams
 from .zerocopy import register_mapping, unregister_mapping
@@ -108,7 +106,7 @@ def _release_replica(key: tuple) -> None:
         del _REPLICAS[key]  # the last reference: the allocation goes back to the allocator
 
 
-class ResidentTokenLoader(PrefetchedIndexedLoader):
+class ResidentTokenLoader(HostPlannedTokenLoader):
     def __init__(self, source: SharedTokenSource, global_batch: int, seq_len: int = 4096, mode: str = "pad",
                  env: DDLEnv | None = None, *, seed: int = 0, pack_order: str = "in_order",
                  token_rows: str | None = None, pad_id: int = 0, depth: int = 2,
@@ -117,19 +115,9 @@ class ResidentTokenLoader(PrefetchedIndexedLoader):
                  chunk_bytes: int = 256 << 20, plan: str = "host"):
         if plan not in ("host", "device"):
             raise ValueError("plan must be 'host' or 'device'")
-        if handoff not in ("host", "device"):
-            raise ValueError("handoff must be 'host' or 'device'")
-        if mode not in ("pad", "pack"):
-            raise ValueError("mode must be 'pad' or 'pack'")
-        if pack_order not in ("in_order", "ffd"):
-            raise ValueError("pack_order must be 'in_order' or 'ffd'")
-        if pack_order != "in_order" and mode != "pack":
-            raise ValueError(f"pack_order={pack_order!r} reorders rows of a PACKED batch; mode={mode!r} has "
-                             "one sequence per row")
         if token_rows is None:  # unset: the host plan sizes every batch exactly, the device plan cannot
             token_rows = "fixed" if plan == "device" and mode == "pack" else "exact"
-        if token_rows not in ("exact", "fixed"):
-            raise ValueError("token_rows must be 'exact' or 'fixed'")
+        check_token_options(mode, pack_order, token_rows, handoff)
         if plan == "device":
             if pack_order == "ffd":
                 raise ValueError("pack_order='ffd' is a sequential bin packing that plan='device' does not build: "
@@ -138,64 +126,34 @@ class ResidentTokenLoader(PrefetchedIndexedLoader):
                 raise ValueError("plan='device' packs into static shapes (the host never learns the row count): "
                                  "token_rows must be 'fixed'; token_rows='exact' needs plan='host'")
         self.plan = plan
-        self.handoff = handoff  # batches take microseconds, not a PCIe transfer: the caller's stream waits
-        self.env = env or DDLEnv()
-        self.W, self.rank = self.env.world_size, self.env.rank
-        self.source, self.seq_len, self.mode = source, int(seq_len), mode
-        self.pack_order, self.token_rows, self.pad_id = pack_order, token_rows, int(pad_id)
-        self.order = EpochOrder(source.n, global_batch, seed)
-        self.GB, self.LB = int(global_batch), self.order.local_batch(self.W)
-        self.out_dtype = torch.int32  # input_ids (the checkpoint's dtype field)
-        if device is None:
-            device = self.env.device or ("cuda" if torch.cuda.is_available() else "cpu")
-        self.device = torch.device(device)
-        if self.device.type == "cuda" and self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
-        self._init_cursor(seed, depth, n_epochs, resume_state)
-
-        lay = self.layout = TokenWindowLayout(self.LB, self.seq_len, source.max_len, 1, source.token_bytes)
-        self._reg = lay.regions()
-        self._hdr_bytes = self._reg["tokens"][0]  # meta + header arrays: everything in front of the tokens
-        # in front of the header: the kernel's descriptor, src_start [LB] i64 + seg_src [max_segments] i64
-        self._desc_bytes = -(-8 * (self.LB + lay.max_segments) // 16) * 16
+        # handoff "device": batches take microseconds, not a PCIe transfer: the caller's stream waits
+        super().__init__(source, global_batch, seq_len, mode, env, seed=seed, pack_order=pack_order,
+                         token_rows=token_rows, pad_id=pad_id, depth=depth, device=device, n_epochs=n_epochs,
+                         resume_state=resume_state, handoff=handoff)
+        lay = self.layout
         if plan == "device" and self.LB * source.max_len > 0x7FFFFFFF:  # the host plan checks every batch instead
             raise ValueError(f"{self.LB} sequences of up to {source.max_len} tokens in one batch can overflow int32 "
                              "cu_seqlens")
-        self._toks = source.tokens.tensor().view(-1)  # keeps the mappings alive
-        self._offs_t = source.offsets.tensor().view(-1)
-        self._offs = self._offs_t.numpy()
-        self.n_elems = int(self._offs[-1]) if source.n else 0
-        self.nbytes = self.n_elems * source.token_bytes
-        self.prep_stream = None
+        self.n_elems = self.nbytes // source.token_bytes
         self._replica_key = None
         self.replica_shared = False
         self.load_s = 0.0
         self.assemble_s = 0.0  # wall time spent in _assemble (host_us_per_step of the benchmark)
         self.profile_every = 0  # > 0: device events around the launch of every profile_every-th step
         self._kernel_evs: list = []
-        self._windows: list = []
-        gpu = self.device.type == "cuda"
+        gpu = self.prep_stream is not None
         if gpu:
-            self.prep_stream = streams.batch_stream(self.device)
             self._replica_key, self._hbm, self.replica_shared = _acquire_replica(
                 source, self.nbytes, self.device, self.prep_stream, float(hbm_fraction), chunk_bytes)
             self.load_s = _REPLICAS[self._replica_key][2]
         if plan == "device":
             self._init_device_plan(gpu)
             return
-        if gpu:
-            win_bytes = self._desc_bytes + self._hdr_bytes  # descriptor + header only: no token ever lands here
-            self._windows = [torch.empty(win_bytes, dtype=torch.uint8, device=self.device)
-                             for _ in range(self.depth + 1)]
-            # pinned slots, one more than the windows: a slot is rewritten only after the copy out of it has
-            # completed (its event), which is normally long done
-            self._slots = [torch.empty(win_bytes, dtype=torch.uint8, pin_memory=True) for _ in range(self.depth + 2)]
-            self._slot_ev = [None] * len(self._slots)
-        else:
-            self._windows = [torch.empty(self._desc_bytes + lay.nbytes, dtype=torch.uint8)
-                             for _ in range(self.depth + 1)]
-            self._slots = self._windows  # the CPU twin writes the header straight into the window
-        self._views = [self._host_views(b) for b in self._slots]
+        # on the GPU a window is descriptor + header only: no token ever lands there
+        self._init_ring(self._desc_bytes + (self._hdr_bytes if gpu else lay.nbytes))
+
+    def _desc_extra(self) -> tuple:
+        return "seg_src", np.int64, self.layout.max_segments  # the corpus element of each segment's first token
 
     def _init_device_plan(self, gpu: bool) -> None:
         """plan="device": the corpus offsets in HBM, a ring of plan windows (the arrays between the launches;
@@ -273,79 +231,32 @@ class ResidentTokenLoader(PrefetchedIndexedLoader):
         """Device address of the corpus replica (None on the CPU, and after ``close``)."""
         return self._hbm.data_ptr() if self._replica_key is not None else None
 
-    def _host_views(self, buf: torch.Tensor) -> dict:
-        """numpy views (and raw addresses) of the descriptor and header arrays at the front of a host buffer."""
-        a = buf.numpy()
-        d, LB = self._desc_bytes, self.LB
-        v = {"src_start": a[:8 * LB].view(np.int64),
-             "seg_src": a[8 * LB:8 * (LB + self.layout.max_segments)].view(np.int64)}
-        for name in ("meta", "offsets", "row_start", "row_end", "seg_offsets"):
-            off, count = self._reg[name]
-            v[name] = a[d + off:d + off + 8 * count].view(np.int64)
-        v["ptr"] = {k: int(x.ctypes.data) for k, x in v.items()}
-        return v
-
     def _assemble(self, t: int):
         if self.plan == "device":
             return self._assemble_device_plan(t)
         t_host = time.perf_counter()
-        e, g = divmod(t, self.order.batches_per_epoch)
-        lay, S, LB, tb = self.layout, self.seq_len, self.LB, self.source.token_bytes
-        offs = self._offs
-        idx = np.asarray(self.order.indices(e, g, self.rank, self.W), dtype=np.int64)
-        lens = offs[idx + 1] - offs[idx]
-        pack = self.mode == "pack"
-        if pack and self.pack_order == "ffd":
-            order, ffd_rows = ffd_order(lens, S)
-            if ffd_rows < in_order_rows(lens, S):  # the producer's rule: FFD is kept only if it wins
-                idx, lens = idx[order], lens[order]
-        gpu = self.prep_stream is not None
-        k = t % len(self._slots)
-        if gpu and self._slot_ev[k] is not None and not self._slot_ev[k].query():
-            self._slot_ev[k].synchronize()  # the H2D copy out of this slot (depth + 2 batches ago)
-        v = self._views[k]
-        p = v["ptr"]
-        v["src_start"][:] = offs[idx]
-        v["offsets"][0] = 0
-        np.cumsum(lens, out=v["offsets"][1:])
-        n_tokens = int(v["offsets"][LB])
-        if n_tokens > self._reg["tokens"][1]:
-            raise ValueError(f"{n_tokens} tokens exceed the layout's {self._reg['tokens'][1]}: the corpus holds a "
-                             "sequence longer than source.max_len")
-        n_rows = n_seg = max_seg = 0
-        if pack:
-            cap = lay.max_segments
-            n_rows, n_seg = _native.runtime().pack_plan(p["offsets"], LB, S, p["row_start"], p["row_end"], cap,
-                                                        p["seg_offsets"], cap)
-            if n_seg:
-                max_seg = int(np.diff(v["seg_offsets"][: n_seg + 1]).max())
-        meta = (n_tokens, n_rows, n_seg, max_seg, 0)
-        v["meta"][:META_FIELDS] = meta
-        win = self._windows[t % len(self._windows)]
-        fixed = self.token_rows == "fixed"
-        if not gpu:
-            _native.runtime().gather_ragged(win.data_ptr() + self._desc_bytes + self._hdr_bytes, p["offsets"],
-                                            self._toks.data_ptr(), self._offs_t.data_ptr(), self.source.n, idx, tb,
-                                            self._reg["tokens"][1], 2)
-            batch = collate_token_window(win[self._desc_bytes:], lay, self.mode, meta, self.pad_id, fixed_rows=fixed)
+        k, v, idx, meta = self._plan(t)
+        n_tokens, n_rows, n_seg, max_seg, _ = meta
+        if self.prep_stream is None:
+            batch = self._cpu_batch(t, v, idx, meta)
             self.assemble_s += time.perf_counter() - t_host
             return batch, None
         if n_tokens > 0x7FFFFFFF:
             raise ValueError(f"{n_tokens} tokens in one batch overflow int32 cu_seqlens")
+        lay, S, LB = self.layout, self.seq_len, self.LB
+        pack, fixed = self.mode == "pack", self.token_rows == "fixed"
         if pack and n_seg:
             v["seg_src"][:n_seg] = segment_sources(v["src_start"], v["offsets"], v["seg_offsets"], n_seg)
         hip, st = _native.hip(), self.prep_stream
         fill = lay.max_segments if (pack and fixed) else 0
         R = max(n_rows, fill) if pack else LB
         timed = self.profile_every > 0 and t % self.profile_every == 0
+        win = self._windows[t % len(self._windows)]
         with streams.on_stream(st):
             w = win.data_ptr()
-            hip.memcpy_h2d(w, self._slots[k].data_ptr(), self._desc_bytes + self._hdr_bytes, st.cuda_stream)
-            if self._slot_ev[k] is None:
-                self._slot_ev[k] = torch.cuda.Event()
-            self._slot_ev[k].record(st)
-            # one allocation for all outputs, laid out as collate_token_window's: memory of its own, so a held
-            # batch survives the rings
+            self._upload(hip, k, win)
+            # one allocation for all outputs (ops.carve_token_outputs): memory of its own, so a held batch
+            # survives the rings
             whole = torch.empty(token_output_bytes(R, S, n_seg if pack else None), dtype=torch.uint8,
                                 device=self.device)
             ids, mask, pos, seg, cu = carve_token_outputs(whole, R, S, n_seg if pack else None)
@@ -360,7 +271,7 @@ class ResidentTokenLoader(PrefetchedIndexedLoader):
                 out_tokens=ids.data_ptr(), attn_mask=mask.data_ptr(), position_ids=pos.data_ptr(), pos_is_i64=True,
                 segment_ids=seg.data_ptr() if pack else 0, cu_seqlens_out=cu.data_ptr() if pack else 0,
                 rows=n_rows if pack else LB, seq_len=S, pad_id=self.pad_id, mode=1 if pack else 0,
-                stream=st.cuda_stream, fill_rows=fill, tok16=tb == 2)
+                stream=st.cuda_stream, fill_rows=fill, tok16=self.source.token_bytes == 2)
             if timed:
                 ev1.record(st)
                 self._kernel_evs.append((ev0, ev1))
@@ -410,9 +321,3 @@ class ResidentTokenLoader(PrefetchedIndexedLoader):
             self._hbm = None
             self._offs_dev = None
             _release_replica(key)
-
-    def __del__(self):  # pragma: no cover - best effort
-        try:
-            self.close()
-        except Exception:
-            pass
