@@ -58,9 +58,14 @@ def main(argv=None):
                          "are device scalars)")
     ap.add_argument("--max-blocks", type=int, default=None,
                     help="zerocopy: grid cap of the gather kernel (0 = uncapped; default: the loader's)")
+    ap.add_argument("--labels", action="store_true",
+                    help="resident / zerocopy: the loader also delivers next-token labels (labels=True); the consumer "
+                         "step is unchanged, so the rate against a run without the flag is the loader's cost")
     a = ap.parse_args(argv)
     zc = a.path in ("zerocopy", "resident")  # producer-free paths
     resident = a.path == "resident"
+    if a.labels and not zc:
+        ap.error("--labels needs --path resident or zerocopy (the producer path has no labels output)")
     if a.plan != "host" and not resident:
         ap.error("--plan device needs --path resident")
     if a.plan == "device" and a.mode == "pack":
@@ -111,11 +116,13 @@ def main(argv=None):
             pack_order = a.pack_order if a.mode == "pack" else "in_order"
             if resident:
                 dl = ddl_amd.ResidentTokenLoader(source, gb, a.seq_len, a.mode, env, pack_order=pack_order,
-                                                 token_rows=a.token_rows, n_epochs=n_epochs, plan=a.plan)
+                                                 token_rows=a.token_rows, n_epochs=n_epochs, plan=a.plan,
+                                                 labels=a.labels)
                 dl.profile_every = a.kernel_sample
             elif zc:
                 dl = ddl_amd.ZeroCopyTokenLoader(source, gb, a.seq_len, a.mode, env, pack_order=pack_order,
-                                                 token_rows=a.token_rows, max_blocks=a.max_blocks, n_epochs=n_epochs)
+                                                 token_rows=a.token_rows, max_blocks=a.max_blocks, n_epochs=n_epochs,
+                                                 labels=a.labels)
             else:
                 producer = TokenBatchProducer(source, gb, a.seq_len, a.mode, pack_order=pack_order,
                                               batches_per_window=a.batches_per_window, host_threads=a.host_threads)
@@ -244,7 +251,7 @@ def main(argv=None):
                     "row_density_est": round(a.batch * mean_len / (rows / a.steps) / a.seq_len, 3),
                     "n_gpus": env.world_size,
                     "steps": a.steps, "ms_per_step": round(1000 * dt / a.steps, 3), "batch_seqs": a.batch,
-                    "token_rows": a.token_rows,
+                    "token_rows": a.token_rows, **({"labels": True} if a.labels else {}),
                     "mean_len": round(mean_len, 1),
                     "token_wire_dtype": "uint16" if source.token_bytes == 2 else "int32",
                     "h2d_token_gbps": round(real_tokens * source.token_bytes / dt / 1e9, 2),

@@ -453,7 +453,95 @@ def tokens_plan(dev, repeats=5) -> None:
         "host_plan_pack_tokens_per_s": round(T_mean / med["host_plan_pack"], 1)}), flush=True)
 
 
+def token_labels(dev, repeats=5) -> None:
+    """Next-token labels at the ``tokens_indexed`` shape (uint16 corpus of 131072 sequences, 2048 per batch, seq_len
+    4096): the indexed and the flat kernel, pad and pack mode, each with labels off, labels on (the fused store)
+    and labels off followed by ``ops.ref_token_labels`` on the device tensors (what a caller writes without the
+    option: a handful of torch kernels and their temporaries). 4 batches issued round-robin at launcher level, the
+    flat stream gathered beforehand. The fused labels are compared with the composition first. One JSON line per
+    repeat and a summary of medians."""
+    from ddl_amd import _native
+    from ddl_amd.ops.kernels import carve_token_outputs, segment_sources, token_output_bytes
+
+    hip = _native.hip()
+    rng = np.random.default_rng(0)
+    n_src, B, S, rot = 131072, 2048, 4096, 4
+    lens = rng.integers(256, 4097, size=n_src)
+    offs = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    corpus = torch.randint(0, 32768, (int(offs[-1]),), dtype=torch.int16, device=dev)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    cases = []
+    for _ in range(rot):
+        idx = rng.choice(n_src, size=B, replace=False).astype(np.int64)
+        start = np.ascontiguousarray(offs[idx])
+        dofs = np.concatenate([[0], np.cumsum(offs[idx + 1] - offs[idx])]).astype(np.int64)
+        rs, re_, so = ops.pack_plan(dofs, S)
+        R, n_seg = len(rs), len(so) - 1
+        seg_src = np.ascontiguousarray(segment_sources(start, dofs, so, n_seg))
+        d = {k: torch.from_numpy(v).to(dev) for k, v in dict(start=start, dofs=dofs, rs=rs, re=re_, so=so,
+                                                             seg_src=seg_src).items()}
+        flat, _ = ops.gather_ragged(corpus, offs, idx)
+        outs = {"pad": carve_token_outputs(torch.empty(token_output_bytes(B, S, None, labels=True), dtype=torch.uint8,
+                                                       device=dev), B, S, None, labels=True),
+                "pack": carve_token_outputs(torch.empty(token_output_bytes(R, S, n_seg, labels=True),
+                                                        dtype=torch.uint8, device=dev), R, S, n_seg, labels=True)}
+        cases.append((d, flat, outs, R, n_seg, int(dofs[-1])))
+
+    def launch(c, kind, mode, labels):
+        d, flat, outs, R, n_seg, _ = c
+        ids, mask, pos, seg, cu, lab = outs[mode]
+        pack = mode == "pack"
+        kw = dict(offsets=0 if pack else d["dofs"].data_ptr(), row_start=d["rs"].data_ptr() if pack else 0,
+                  row_end=d["re"].data_ptr() if pack else 0, seg_offsets=d["so"].data_ptr() if pack else 0,
+                  n_seg=n_seg if pack else 0, out_tokens=ids.data_ptr(), attn_mask=mask.data_ptr(),
+                  position_ids=pos.data_ptr(), pos_is_i64=True, segment_ids=seg.data_ptr() if pack else 0,
+                  cu_seqlens_out=cu.data_ptr() if pack else 0, rows=R if pack else B, seq_len=S, pad_id=0,
+                  mode=1 if pack else 0, stream=stream, tok16=True, labels=lab.data_ptr() if labels else 0)
+        if kind == "indexed":
+            hip.pad_pack_tokens_indexed(corpus=corpus.data_ptr(), corpus_elems=corpus.numel(),
+                                        src_start=d["start"].data_ptr(), seg_src=d["seg_src"].data_ptr() if pack else 0,
+                                        **kw)
+        else:
+            hip.pad_pack_tokens(tokens=flat.data_ptr(), **kw)
+
+    def composed(c, kind, mode):
+        launch(c, kind, mode, False)
+        ids, mask, _, seg, _, _ = c[2][mode]
+        return ops.ref_token_labels(ids, mask, seg)
+
+    variants = [(kind, mode) for kind in ("indexed", "flat") for mode in ("pad", "pack")]
+    for c in cases:  # the fused labels are the composition's
+        for kind, mode in variants:
+            launch(c, kind, mode, True)
+            ref = composed(c, kind, mode)
+            torch.cuda.synchronize()
+            assert torch.equal(c[2][mode][5], ref), f"{kind} {mode}: fused labels differ from ref_token_labels"
+    runs = []
+    for r in range(repeats):
+        t = {}
+        for kind, mode in variants:
+            t[f"{kind}_{mode}_off"] = rotating([lambda c=c: launch(c, kind, mode, False) for c in cases])
+            t[f"{kind}_{mode}_on"] = rotating([lambda c=c: launch(c, kind, mode, True) for c in cases])
+            t[f"{kind}_{mode}_off_plus_torch"] = rotating([lambda c=c: composed(c, kind, mode) for c in cases])
+        runs.append(t)
+        print(json.dumps({"kernel": "token labels", "repeat": r,
+                          **{k + "_us": round(v * 1e6, 2) for k, v in t.items()}}), flush=True)
+    med = {k: float(np.median([t[k] for t in runs])) for k in runs[0]}
+    R_mean = float(np.mean([c[3] for c in cases]))
+    T_mean = float(np.mean([c[5] for c in cases]))
+    print(json.dumps({
+        "kernel": "token labels summary", "sequences": B, "seq_len": S, "token_dtype": "uint16", "pack_rows": R_mean,
+        "tokens": T_mean, "repeats": repeats, **{k + "_us_median": round(v * 1e6, 2) for k, v in med.items()},
+        **{f"{kind}_{mode}_on_over_off": round(med[f"{kind}_{mode}_on"] / med[f"{kind}_{mode}_off"], 3)
+           for kind, mode in variants},
+        **{f"{kind}_{mode}_on_over_torch": round(med[f"{kind}_{mode}_on"] / med[f"{kind}_{mode}_off_plus_torch"], 3)
+           for kind, mode in variants}}), flush=True)
+
+
 if __name__ == "__main__":
+    if "--only-token-labels" in sys.argv[1:]:  # profiles/token_labels/
+        token_labels(torch.device("cuda", 0))
+        sys.exit(0)
     if "--only-tokens-indexed" in sys.argv[1:]:  # the one case, e.g. for profiles/resident_tokens/
         tokens_indexed(torch.device("cuda", 0))
         sys.exit(0)

@@ -707,8 +707,11 @@ PYBIND11_MODULE(_ddl_hip, m) {
       [](uintptr_t tokens, uintptr_t offsets, uintptr_t row_start, uintptr_t row_end, uintptr_t seg_offsets,
          int64_t n_seg, uintptr_t out_tokens, uintptr_t attn_mask, uintptr_t position_ids, bool pos_is_i64,
          uintptr_t segment_ids, uintptr_t cu_seqlens_out, int64_t rows, int64_t seq_len, int pad_id, int mode,
-         uintptr_t stream, int64_t fill_rows, uintptr_t dev_counts, bool tok16) {
+         uintptr_t stream, int64_t fill_rows, uintptr_t dev_counts, bool tok16, uintptr_t labels,
+         int32_t ignore_index) {
         ddl::TokenSpec sp{};
+        sp.labels = as_ptr<int64_t>(labels);
+        sp.ignore_index = ignore_index;
         sp.tok16 = tok16 ? 1 : 0;
         sp.fill_rows = fill_rows;
         sp.dev_counts = as_ptr<const int64_t>(dev_counts);
@@ -734,15 +737,17 @@ PYBIND11_MODULE(_ddl_hip, m) {
       py::arg("n_seg"), py::arg("out_tokens"), py::arg("attn_mask"), py::arg("position_ids"), py::arg("pos_is_i64"),
       py::arg("segment_ids"), py::arg("cu_seqlens_out"), py::arg("rows"), py::arg("seq_len"), py::arg("pad_id"),
       py::arg("mode"), py::arg("stream"), py::arg("fill_rows") = 0, py::arg("dev_counts") = 0,
-      py::arg("tok16") = false);
+      py::arg("tok16") = false, py::arg("labels") = 0, py::arg("ignore_index") = -100);
   m.def(
       "pad_pack_tokens_indexed",
       [](uintptr_t corpus, int64_t corpus_elems, uintptr_t src_start, uintptr_t seg_src, uintptr_t offsets,
          uintptr_t row_start, uintptr_t row_end, uintptr_t seg_offsets, int64_t n_seg, uintptr_t out_tokens,
          uintptr_t attn_mask, uintptr_t position_ids, bool pos_is_i64, uintptr_t segment_ids, uintptr_t cu_seqlens_out,
          int64_t rows, int64_t seq_len, int pad_id, int mode, uintptr_t stream, int64_t fill_rows, bool tok16,
-         uintptr_t dev_counts, int64_t cu_cap) {
+         uintptr_t dev_counts, int64_t cu_cap, uintptr_t labels, int32_t ignore_index) {
         ddl::TokenSpec sp{};
+        sp.labels = as_ptr<int64_t>(labels);
+        sp.ignore_index = ignore_index;
         sp.tok16 = tok16 ? 1 : 0;
         sp.fill_rows = fill_rows;
         sp.dev_counts = as_ptr<const int64_t>(dev_counts);
@@ -771,7 +776,7 @@ PYBIND11_MODULE(_ddl_hip, m) {
       py::arg("attn_mask"), py::arg("position_ids"), py::arg("pos_is_i64"), py::arg("segment_ids"),
       py::arg("cu_seqlens_out"), py::arg("rows"), py::arg("seq_len"), py::arg("pad_id"), py::arg("mode"),
       py::arg("stream"), py::arg("fill_rows") = 0, py::arg("tok16") = false, py::arg("dev_counts") = 0,
-      py::arg("cu_cap") = 0);
+      py::arg("cu_cap") = 0, py::arg("labels") = 0, py::arg("ignore_index") = -100);
   m.def(
       "token_batch_descriptor",
       [](uintptr_t corpus_offsets, int64_t n_corpus, int mode, uintptr_t idx, int64_t base, std::vector<uint64_t> keys,

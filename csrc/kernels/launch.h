@@ -102,6 +102,11 @@ struct TokenSpec {
   // `rows` / `n_seg`, so plan and pack are two launches with no host round trip (fill_rows = the plan's
   // row capacity; n_rows < 0, an overflowed plan, writes every row as padding)
   const int64_t* dev_counts;
+  // next-token labels [R, S] i64 (or null: off), what cross_entropy(ignore_index) takes: labels[r, p] =
+  // out_tokens[r, p + 1] where p + 1 is a data position of the same row and (pack mode) of the same segment,
+  // ignore_index everywhere else (a row's last position, a segment's last token, padding positions and rows)
+  int64_t* labels;
+  int32_t ignore_index;
 };
 int pad_pack_tokens(const TokenSpec& spec, hipStream_t st);
 
@@ -135,8 +140,8 @@ int pad_pack_tokens_multi(const TokenSpec* specs, int n, hipStream_t st);
 // row_start / row_end / seg_offsets in pack mode) are positions of that virtual stream as for pad_pack_tokens.
 // corpus: int32, or uint16 when spec.tok16, corpus_elems elements; src_start [B] (pad mode) and seg_src
 // [n_seg] (pack mode: the corpus element of each segment's first token) are device-readable. Outputs of a row
-// width that is a multiple of 4 must be 16-byte aligned (the mask 4-byte). Block 0 writes cu_seqlens_out even
-// when there is no row.
+// width that is a multiple of 4 must be 16-byte aligned (the mask 4-byte; the labels 16, like i64 position ids).
+// Block 0 writes cu_seqlens_out even when there is no row.
 // A plan built on the device (pack mode, spec.dev_counts = pack_plan_device's counts): the kernel reads
 // {n_rows, n_seg} there instead of spec.rows / spec.n_seg, the grid is sized by spec.fill_rows (> 0, the plan's
 // row capacity) and n_rows < 0, an overflowed plan, writes every row as padding.

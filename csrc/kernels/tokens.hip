@@ -52,7 +52,20 @@ __device__ __forceinline__ void emit4(const TokenSpec& sp, const TiRow& r, At se
       seg[k] = -1;
     }
   }
-  ti_store4(sp, r.row, r.p0, tok, pos, seg, msk);
+  int32_t lab[kTiLane];
+  if (sp.labels) {  // block-uniform, like attn_mask
+    // position p's label is the token at p + 1 where that is data of the same row and (pack) segment: the lane's
+    // own next token, and for its last position src[p0 + 4], one more load next to the fourth (p0 + 4 < len keeps
+    // it inside the row's span of the stream; seg_at(s + 1) exists, s < n_seg being position p0 + 3's segment)
+#pragma unroll
+    for (int k = 0; k + 1 < kTiLane; ++k)
+      lab[k] = msk[k + 1] && (sp.mode == 0 || seg[k + 1] == seg[k]) ? tok[k + 1] : sp.ignore_index;
+    const int64_t p4 = r.p0 + kTiLane;
+    bool has = p4 < r.len;
+    if (has && sp.mode != 0) has = r.start + p4 < seg_at(s + 1);
+    lab[kTiLane - 1] = has ? (sp.tok16 ? static_cast<int32_t>(src16[p4]) : src[p4]) : sp.ignore_index;
+  }
+  ti_store4(sp, r.row, r.p0, tok, pos, seg, msk, lab);
 }
 
 __device__ __forceinline__ void pad_pack_block(const TokenSpec& spec, uint32_t bx, int32_t chunks, int64_t* seg_lds) {
@@ -211,6 +224,7 @@ int pad_pack_tokens(const TokenSpec& spec, hipStream_t st) {
   if (grid == 0) return 0;
   if (spec.mode == 0 && !spec.offsets) return -2;
   if (spec.mode == 1 && (!spec.row_start || !spec.row_end || !spec.seg_offsets)) return -2;
+  if (spec.seq_len % kTiLane == 0 && reinterpret_cast<uintptr_t>(spec.labels) % 16) return -2;  // 16-byte stores
   if (grid < 0) return -4;
   hipLaunchKernelGGL(pad_pack_kernel, dim3(static_cast<uint32_t>(grid)), dim3(kTiThreads), 0, st, spec,
                      static_cast<int32_t>(ti_chunks(spec.seq_len)));
@@ -227,6 +241,7 @@ int pad_pack_tokens_multi(const TokenSpec* specs, int n, hipStream_t st) {
       if (sp.seq_len <= 0 || (sp.mode == 0 && !sp.offsets) ||
           (sp.mode == 1 && (!sp.row_start || !sp.row_end || !sp.seg_offsets)))
         return -2;
+      if (sp.seq_len % kTiLane == 0 && reinterpret_cast<uintptr_t>(sp.labels) % 16) return -2;
       if (j > 0 && sp.seq_len != seq_len) return -2;  // one chunking for the launch
       seq_len = sp.seq_len;
       if (sp.rows > max_rows) max_rows = sp.rows;

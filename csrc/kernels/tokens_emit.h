@@ -6,7 +6,7 @@
 //
 // Grid: one workgroup per (row, chunk of kTiSpan = 512 positions), so a 64 x 4096 batch is 512 workgroups. A lane
 // writes 4 consecutive positions: 16-byte stores of ids / i32 position ids / segment ids (2 x 16 B for i64 position
-// ids) and a 4-byte mask store, per-element stores where the row width is no multiple of 4. Pack mode copies the
+// ids, and for the i64 next-token labels where they are asked for) and a 4-byte mask store, per-element stores where the row width is no multiple of 4. Pack mode copies the
 // segment starts into LDS once per workgroup when n_seg + 1 <= kTiSegCap and binary-searches there, global memory
 // otherwise; a lane searches once and then advances.
 #pragma once
@@ -61,9 +61,11 @@ __device__ __forceinline__ TiRow ti_prologue(TokenSpec& sp, uint32_t bx, int32_t
   return r;
 }
 
-// The store half: 4 values of every output at (row, p0), as vectors where ti_vector_store allows
+// The store half: 4 values of every output at (row, p0), as vectors where ti_vector_store allows. lab: the lane's
+// 4 next-token labels, read (and stored, widened to i64: 2 x 16 B) only where sp.labels is set (block-uniform)
 __device__ __forceinline__ void ti_store4(const TokenSpec& sp, int64_t row, int64_t p0, const int32_t* tok,
-                                          const int32_t* pos, const int32_t* seg, const uint8_t* msk) {
+                                          const int32_t* pos, const int32_t* seg, const uint8_t* msk,
+                                          const int32_t* lab) {
   const int64_t S = sp.seq_len;
   const int64_t o = row * S + p0;
   if (ti_vector_store(p0, S)) {
@@ -84,6 +86,10 @@ __device__ __forceinline__ void ti_store4(const TokenSpec& sp, int64_t row, int6
     }
     if (sp.segment_ids)
       *reinterpret_cast<int4*>(sp.segment_ids + o) = make_int4(seg[0], seg[1], seg[2], seg[3]);
+    if (sp.labels) {
+      *reinterpret_cast<longlong2*>(sp.labels + o) = make_longlong2(lab[0], lab[1]);
+      *reinterpret_cast<longlong2*>(sp.labels + o + 2) = make_longlong2(lab[2], lab[3]);
+    }
   } else {
     for (int k = 0; k < kTiLane && p0 + k < S; ++k) {
       sp.out_tokens[o + k] = tok[k];
@@ -95,6 +101,7 @@ __device__ __forceinline__ void ti_store4(const TokenSpec& sp, int64_t row, int6
           static_cast<int32_t*>(sp.position_ids)[o + k] = pos[k];
       }
       if (sp.segment_ids) sp.segment_ids[o + k] = seg[k];
+      if (sp.labels) sp.labels[o + k] = lab[k];
     }
   }
 }

@@ -1,7 +1,8 @@
 // Index arithmetic of the pad/pack kernels, shared with host code. The constants, the grid, the lane origin, the
 // row length, the vector-store predicate and the search serve the flat kernel (tokens.hip) and the indexed one
 // (tokens_indexed.hip) alike (their shared device half is tokens_emit.h); ti_lane4 is the indexed kernel's lane
-// loop, which csrc/kernels/tests/tokens_indexed_check.cpp replays under ASan/UBSan.
+// loop, which csrc/kernels/tests/tokens_indexed_check.cpp replays under ASan/UBSan; ti_labels4 is its next-token
+// label arithmetic (tests/token_labels_check.cpp).
 // Plain inline functions: __host__ __device__ under hipcc, plain under g++ (this header includes nothing of HIP).
 //
 // The indexed kernel writes what pad_pack_tokens (tokens.hip) writes for the VIRTUAL flat stream
@@ -121,6 +122,31 @@ DDL_TI_HD void ti_lane4(int mode, int64_t p0, int64_t start, int64_t len, int64_
       out->seg[k] = static_cast<int32_t>(s);
     }
   }
+}
+
+// Next-token labels of the lane's 4 positions: position p has a target iff p + 1 is a data position of the row
+// (p + 1 < len <= S) and, in pack mode, of p's segment; every other label is the caller's ignore_index.
+struct TiLabel4 {
+  uint8_t has[kTiLane];  // 1: the label of p0 + k is the token at p0 + k + 1 (k < 3: the lane's own token k + 1)
+  int64_t src4;          // has[3]: the corpus element of the token at p0 + 4, else -1 (nothing is read)
+};
+
+// `ln` = ti_lane4 of the same arguments. The token at p0 + 4 of the same segment is corpus element ln.src[3] + 1:
+// in pad mode p0 + 4 < len_row, in pack mode g + 1 < seg_at(s + 1) (entry n_seg exists), so it lies inside the
+// selected sequence that position p0 + 3 was read from, and the kernel's bounded-reads contract holds.
+template <typename SegAt>
+DDL_TI_HD void ti_labels4(int mode, int64_t p0, int64_t start, int64_t len, SegAt seg_at, const TiLane4& ln,
+                          TiLabel4* out) {
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+  for (int k = 0; k + 1 < kTiLane; ++k)
+    out->has[k] = ln.msk[k + 1] != 0 && (mode == 0 || ln.seg[k + 1] == ln.seg[k]) ? 1 : 0;
+  const int64_t p4 = p0 + kTiLane;
+  bool has = p4 < len;  // then p0 + 3 is data as well: ln.src[3] and (pack mode) ln.seg[3] are its
+  if (has && mode != 0) has = start + p4 < seg_at(static_cast<int64_t>(ln.seg[kTiLane - 1]) + 1);
+  out->has[kTiLane - 1] = has ? 1 : 0;
+  out->src4 = has ? ln.src[kTiLane - 1] + 1 : -1;
 }
 
 }  // namespace ddl

@@ -15,7 +15,9 @@
 //   pad   src_start[row] + p,                    p < len_row
 //   pack  seg_src[s] + (g - seg_offsets[s]),     seg_offsets[s] <= g < seg_offsets[s + 1]
 // i.e. only inside [src_start[i], src_start[i] + len_i) of the selected sequences (a segment is a piece of one
-// sequence). An empty sequence, a padding position and a padding row read nothing. On top of that contract an
+// sequence). An empty sequence, a padding position and a padding row read nothing. With labels the lane also
+// reads the token at p0 + 4, the target of its last position, only where p0 + 4 < len and (pack) g + 1 lies in
+// the same segment: the element after its fourth, inside the same bounds (ti_labels4). On top of that contract an
 // element index outside [0, corpus_elems) -- a corrupt descriptor -- is not dereferenced: pad_id is written.
 // Bounded writes: workgroup (row, chunk) writes positions [chunk * 512, min((chunk + 1) * 512, S)) of row
 // `row` < max(rows, fill_rows) of every output, each exactly once (the vector path only where all 4 positions
@@ -56,23 +58,34 @@ __global__ void __launch_bounds__(kTiThreads) pad_pack_indexed_kernel(IndexedSpe
   const int64_t src0 = sp.mode == 0 && r.row < sp.rows ? ix.src_start[r.row] : 0;
   const int32_t* c32 = static_cast<const int32_t*>(ix.corpus);
   const uint16_t* c16 = static_cast<const uint16_t*>(ix.corpus);
+  const bool labels = sp.labels != nullptr;  // block-uniform, like attn_mask
   TiLane4 ln;
-  if (r.staged)
-    ti_lane4(sp.mode, r.p0, r.start, r.len, src0, sp.n_seg, [&](int64_t i) { return seg_lds[i]; },
-             [&](int64_t i) { return src_lds[i]; }, &ln);
-  else
-    ti_lane4(sp.mode, r.p0, r.start, r.len, src0, sp.n_seg, [&](int64_t i) { return sp.seg_offsets[i]; },
-             [&](int64_t i) { return ix.seg_src[i]; }, &ln);
-  int32_t tok[kTiLane];
-#pragma unroll
-  for (int k = 0; k < kTiLane; ++k) {
-    const int64_t e = ln.src[k];
-    if (static_cast<uint64_t>(e) < static_cast<uint64_t>(ix.corpus_elems))  // -1 (padding) fails it too
-      tok[k] = sp.tok16 ? static_cast<int32_t>(__builtin_nontemporal_load(c16 + e)) : __builtin_nontemporal_load(c32 + e);
-    else
-      tok[k] = sp.pad_id;  // a corrupt descriptor's element outside the corpus is not dereferenced
+  TiLabel4 lb;
+  if (r.staged) {
+    const auto seg_at = [&](int64_t i) { return seg_lds[i]; };
+    ti_lane4(sp.mode, r.p0, r.start, r.len, src0, sp.n_seg, seg_at, [&](int64_t i) { return src_lds[i]; }, &ln);
+    if (labels) ti_labels4(sp.mode, r.p0, r.start, r.len, seg_at, ln, &lb);
+  } else {
+    const auto seg_at = [&](int64_t i) { return sp.seg_offsets[i]; };
+    ti_lane4(sp.mode, r.p0, r.start, r.len, src0, sp.n_seg, seg_at, [&](int64_t i) { return ix.seg_src[i]; }, &ln);
+    if (labels) ti_labels4(sp.mode, r.p0, r.start, r.len, seg_at, ln, &lb);
   }
-  ti_store4(sp, r.row, r.p0, tok, ln.pos, ln.seg, ln.msk);
+  const auto load = [&](int64_t e) {
+    if (static_cast<uint64_t>(e) < static_cast<uint64_t>(ix.corpus_elems))  // -1 (padding) fails it too
+      return sp.tok16 ? static_cast<int32_t>(__builtin_nontemporal_load(c16 + e)) : __builtin_nontemporal_load(c32 + e);
+    return sp.pad_id;  // a corrupt descriptor's element outside the corpus is not dereferenced
+  };
+  int32_t tok[kTiLane], lab[kTiLane];
+#pragma unroll
+  for (int k = 0; k < kTiLane; ++k) tok[k] = load(ln.src[k]);
+  if (labels) {
+    // the label of position p is the token at p + 1: the lane's own next token, and for its last position one
+    // more element, adjacent to the lane's fourth (the neighbouring lane loads it as its first)
+#pragma unroll
+    for (int k = 0; k + 1 < kTiLane; ++k) lab[k] = lb.has[k] ? tok[k + 1] : sp.ignore_index;
+    lab[kTiLane - 1] = lb.has[kTiLane - 1] ? load(lb.src4) : sp.ignore_index;
+  }
+  ti_store4(sp, r.row, r.p0, tok, ln.pos, ln.seg, ln.msk, lab);
 }
 
 }  // namespace
@@ -100,7 +113,8 @@ int pad_pack_tokens_indexed(const TokenSpec& spec, const void* corpus, int64_t c
   if (reinterpret_cast<uintptr_t>(corpus) % elem) return -2;
   if (spec.seq_len % kTiLane == 0) {  // the vector path: 16-byte stores of the 4- and 8-byte outputs, 4-byte of the mask
     if (reinterpret_cast<uintptr_t>(spec.out_tokens) % 16 || reinterpret_cast<uintptr_t>(spec.position_ids) % 16 ||
-        reinterpret_cast<uintptr_t>(spec.segment_ids) % 16 || reinterpret_cast<uintptr_t>(spec.attn_mask) % 4)
+        reinterpret_cast<uintptr_t>(spec.segment_ids) % 16 || reinterpret_cast<uintptr_t>(spec.attn_mask) % 4 ||
+        reinterpret_cast<uintptr_t>(spec.labels) % 16)
       return -2;
   }
   const int64_t grid = ti_grid(dev_plan ? 0 : spec.rows, spec.fill_rows, spec.seq_len, has_cu);

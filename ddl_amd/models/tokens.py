@@ -396,38 +396,47 @@ def drop_cached_views(base_ptrs) -> int:
 
 
 def collate_token_window(buf: torch.Tensor, layout: TokenWindowLayout, mode: str, meta, pad_id: int = 0,
-                         sub: int = 0, fixed_rows: bool = False):
+                         sub: int = 0, fixed_rows: bool = False, labels: bool = False, ignore_index: int = -100):
     """Expand sub-batch ``sub`` of one (device or host) token window into model inputs; ``meta`` is the
     window's meta table (flat, META_FIELDS per sub-batch: the stager's host copy, or the host window).
     ``fixed_rows`` (pack mode): every batch has ``layout.max_segments`` rows, the rows past the packed
-    ones are padding (static shapes), and ``n_rows`` gives the packed count."""
+    ones are padding (static shapes), and ``n_rows`` gives the packed count. ``labels``: the batch gains
+    ``labels``, the next-token targets (``ops.ref_token_labels``), written by the same kernel."""
     from .. import ops
+    from ..ops.kernels import _label_args, _stream_handle
 
+    ignore_index = _label_args(labels, ignore_index)
     v = _cached_views(buf.view(-1), layout, sub)
     n_tokens, n_rows, n_seg, max_seqlen, tok0 = (int(x) for x in meta[META_FIELDS * sub:META_FIELDS * (sub + 1)])
     tokens = v["tokens"][tok0:tok0 + n_tokens]
     if mode == "pad":
-        ids, mask, pos = ops.pad_tokens(tokens, v["offsets"], layout.seq_len, pad_id)
+        ids, mask, pos, *lab = ops.pad_tokens(tokens, v["offsets"], layout.seq_len, pad_id, labels=labels,
+                                              ignore_index=ignore_index)
         # n_tokens: tokens shipped (pad mode truncates sequences longer than seq_len: mask.sum() can be less)
-        return {"input_ids": ids, "attention_mask": mask, "position_ids": pos, "n_tokens": n_tokens}
+        batch = {"input_ids": ids, "attention_mask": mask, "position_ids": pos, "n_tokens": n_tokens}
+        if labels:
+            batch["labels"] = lab[0]
+        return batch
     fill = layout.max_segments if fixed_rows else 0
     extra = {"n_rows": n_rows} if fixed_rows else {}
     if not tokens.is_cuda:
         ids, mask, pos, seg = ops.ref_pack_tokens(tokens, v["row_start"][:n_rows].numpy(),
                                                   v["row_end"][:n_rows].numpy(), v["seg_offsets"][: n_seg + 1].numpy(),
                                                   layout.seq_len, pad_id, fill_rows=fill)
+        if labels:
+            extra["labels"] = ops.ref_token_labels(ids, mask, seg, ignore_index)
         return {"input_ids": ids, "attention_mask": mask, "position_ids": pos, "segment_ids": seg,
                 "cu_seqlens": v["seg_offsets"][: n_seg + 1].to(torch.int32), "max_seqlen": max_seqlen,
                 "n_tokens": n_tokens, **extra}
     dev = tokens.device
     s = layout.seq_len
-    # one allocation for all five outputs (ops.carve_token_outputs). cu_seqlens is written by the kernel into
+    # one allocation for all outputs (ops.carve_token_outputs). cu_seqlens is written by the kernel into
     # memory of its own: a view of the staging buffer would be overwritten when it is re-staged
     R = max(n_rows, fill)
-    whole = torch.empty(ops.token_output_bytes(R, s, n_seg), dtype=torch.uint8, device=dev)
-    ids, mask, pos, seg, cu = ops.carve_token_outputs(whole, R, s, n_seg)
-    from ..ops.kernels import _stream_handle
-
+    whole = torch.empty(ops.token_output_bytes(R, s, n_seg, labels=labels), dtype=torch.uint8, device=dev)
+    ids, mask, pos, seg, cu, *lab = ops.carve_token_outputs(whole, R, s, n_seg, labels=labels)
+    if labels:
+        extra["labels"] = lab[0]
     if n_tokens > 0x7FFFFFFF:
         raise ValueError(f"{n_tokens} tokens in one batch overflow int32 cu_seqlens")
     if R == 0:
@@ -438,7 +447,8 @@ def collate_token_window(buf: torch.Tensor, layout: TokenWindowLayout, mode: str
             row_end=v["row_end"].data_ptr(), seg_offsets=v["seg_offsets"].data_ptr(), n_seg=n_seg,
             out_tokens=ids.data_ptr(), attn_mask=mask.data_ptr(), position_ids=pos.data_ptr(), pos_is_i64=True,
             segment_ids=seg.data_ptr(), cu_seqlens_out=cu.data_ptr(), rows=n_rows, seq_len=s, pad_id=pad_id, mode=1,
-            stream=_stream_handle(None), fill_rows=fill, tok16=layout.token_bytes == 2)
+            stream=_stream_handle(None), fill_rows=fill, tok16=layout.token_bytes == 2,
+            labels=lab[0].data_ptr() if labels else 0, ignore_index=ignore_index)
     return {"input_ids": ids, "attention_mask": mask, "position_ids": pos, "segment_ids": seg, "cu_seqlens": cu,
             "max_seqlen": max_seqlen, "n_tokens": n_tokens, **extra}
 

@@ -600,25 +600,60 @@ def ref_pad_tokens(tokens: torch.Tensor, offsets: torch.Tensor, seq_len: int, pa
     return out, mask, pos
 
 
+def ref_token_labels(input_ids: torch.Tensor, attention_mask: torch.Tensor, segment_ids: torch.Tensor | None = None,
+                     ignore_index: int = -100) -> torch.Tensor:
+    """Next-token labels of a token batch (int64 [R, S], what ``cross_entropy(..., ignore_index=ignore_index)``
+    takes), with torch ops on the batch's device -- the definition the kernels' ``labels=True`` implements::
+
+        labels[r, p] = input_ids[r, p + 1]   if p + 1 < S and attention_mask[r, p + 1] == 1
+                                             and (pad mode or segment_ids[r, p + 1] == segment_ids[r, p])
+                     = ignore_index          otherwise
+
+    ``segment_ids`` None: pad mode. So the last position of a row (a pad row truncated at S included), the last
+    token of every segment (each ``seq_len`` chunk of an over-long packed sequence is its own segment), a
+    one-token segment, and every padding position and padding row are ``ignore_index``."""
+    ids = input_ids.to(torch.int64)
+    lab = torch.full_like(ids, int(ignore_index))
+    if ids.shape[-1] > 1:
+        ok = attention_mask[..., 1:] != 0
+        if segment_ids is not None:
+            ok = ok & (segment_ids[..., 1:] == segment_ids[..., :-1])
+        lab[..., :-1] = torch.where(ok, ids[..., 1:], lab[..., :-1])
+    return lab
+
+
+def _label_args(labels: bool, ignore_index: int) -> int:
+    """The checked ``ignore_index`` (the kernels carry it as an int32)."""
+    ignore_index = int(ignore_index)
+    if labels and not -(1 << 31) <= ignore_index < (1 << 31):
+        raise ValueError(f"ignore_index={ignore_index} does not fit int32")
+    return ignore_index
+
+
 def pad_tokens(tokens: torch.Tensor, offsets: torch.Tensor, seq_len: int, pad_id: int = 0,
-               position_dtype=torch.int64, stream=None):
+               position_dtype=torch.int64, stream=None, labels: bool = False, ignore_index: int = -100):
     """Ragged token stream (int32, or 16-bit ids widened by the kernel) + [B+1] int64 offsets ->
-    (tokens [B,S] i32, mask u8 [B,S], position ids [B,S])."""
+    (tokens [B,S] i32, mask u8 [B,S], position ids [B,S]); ``labels=True`` appends the next-token labels (int64
+    [B,S], ``ref_token_labels``), written by the same kernel."""
     if (tokens.dtype != torch.int32 and tokens.dtype not in _TOK16) or offsets.dtype != torch.int64:
         raise TypeError("tokens must be int32 / 16-bit and offsets int64")
+    ignore_index = _label_args(labels, ignore_index)
     if not tokens.is_cuda:
-        return ref_pad_tokens(tokens, offsets, seq_len, pad_id, position_dtype)
+        r = ref_pad_tokens(tokens, offsets, seq_len, pad_id, position_dtype)
+        return (*r, ref_token_labels(r[0], r[1], None, ignore_index)) if labels else r
     b = offsets.numel() - 1
     dev = tokens.device
     out = torch.empty((b, seq_len), dtype=torch.int32, device=dev)
     mask = torch.empty((b, seq_len), dtype=torch.uint8, device=dev)
     pos = torch.empty((b, seq_len), dtype=position_dtype, device=dev)
+    lab = torch.empty((b, seq_len), dtype=torch.int64, device=dev) if labels else None
     _native.hip().pad_pack_tokens(
         tokens=tokens.data_ptr(), offsets=offsets.data_ptr(), row_start=0, row_end=0, seg_offsets=0, n_seg=0,
         out_tokens=out.data_ptr(), attn_mask=mask.data_ptr(), position_ids=pos.data_ptr(),
         pos_is_i64=position_dtype == torch.int64, segment_ids=0, cu_seqlens_out=0, rows=b, seq_len=seq_len,
-        pad_id=pad_id, mode=0, stream=_stream_handle(stream), tok16=tokens.dtype in _TOK16)
-    return out, mask, pos
+        pad_id=pad_id, mode=0, stream=_stream_handle(stream), tok16=tokens.dtype in _TOK16,
+        labels=lab.data_ptr() if labels else 0, ignore_index=ignore_index)
+    return (out, mask, pos, lab) if labels else (out, mask, pos)
 
 
 def pack_plan(seq_offsets: np.ndarray, seq_len: int, max_rows: int | None = None):
@@ -714,7 +749,8 @@ def pack_capacity(n_seq: int, n_tokens: int, seq_len: int) -> tuple[int, int]:
 
 
 def pack_tokens_device(tokens: torch.Tensor, offsets: torch.Tensor, seq_len: int, pad_id: int = 0,
-                       position_dtype=torch.int64, max_rows: int | None = None, stream=None) -> dict:
+                       position_dtype=torch.int64, max_rows: int | None = None, stream=None, labels: bool = False,
+                       ignore_index: int = -100) -> dict:
     """Pack with the plan built ON THE DEVICE: two launches (``pack_plan_device``, then the pack kernel
     reading the plan's row count from device memory), no host round trip, static output shapes.
 
@@ -723,9 +759,11 @@ def pack_tokens_device(tokens: torch.Tensor, offsets: torch.Tensor, seq_len: int
     plan's are padding (pad_id, mask 0, position 0, segment -1). Returns a dict: ``input_ids``,
     ``attention_mask``, ``position_ids``, ``segment_ids``, ``cu_seqlens`` (int32, capacity max_segs + 1; only
     the first n_seg + 1 entries are written), ``counts`` (device int64 [n_rows, n_seg]; n_rows = -1 if max_rows
-    was too small, every row then padding). Reference of the plan: ``pack_plan`` (host, runtime/arena.cpp).
+    was too small, every row then padding). ``labels=True`` adds ``labels`` (``ref_token_labels``; all
+    ``ignore_index`` for an overflowed plan). Reference of the plan: ``pack_plan`` (host, runtime/arena.cpp).
     Graph-capturable: nothing in it synchronises with the host.
     """
+    ignore_index = _label_args(labels, ignore_index)
     if (tokens.dtype != torch.int32 and tokens.dtype not in _TOK16) or offsets.dtype != torch.int64:
         raise TypeError("tokens must be int32 / 16-bit and offsets int64")
     n = offsets.numel() - 1
@@ -743,8 +781,11 @@ def pack_tokens_device(tokens: torch.Tensor, offsets: torch.Tensor, seq_len: int
         cu = torch.zeros(max_segs + 1, dtype=torch.int32)
         cu[:len(so)] = torch.from_numpy(so.astype(np.int32))
         counts = torch.tensor([len(rs) if ok else -1, len(so) - 1], dtype=torch.int64)
-        return {"input_ids": out[:R], "attention_mask": mask[:R], "position_ids": pos[:R], "segment_ids": seg[:R],
-                "cu_seqlens": cu, "counts": counts}
+        r = {"input_ids": out[:R], "attention_mask": mask[:R], "position_ids": pos[:R], "segment_ids": seg[:R],
+             "cu_seqlens": cu, "counts": counts}
+        if labels:
+            r["labels"] = ref_token_labels(r["input_ids"], r["attention_mask"], r["segment_ids"], ignore_index)
+        return r
     if not offsets.is_cuda or offsets.device != dev:
         raise ValueError("offsets must be on the tokens' device (use pack_tokens for host offsets)")
     h = _native.hip()
@@ -752,7 +793,7 @@ def pack_tokens_device(tokens: torch.Tensor, offsets: torch.Tensor, seq_len: int
     # one allocation for the plan, its scratch and the five outputs (16-byte aligned regions)
     pb = 8 if position_dtype == torch.int64 else 4
     sizes = [8 * (max_segs + 1), 8 * max(R, 1), 8 * max(R, 1), 16, 4 * h.pack_plan_scratch_ints(max_segs, R),
-             4 * R * S, R * S, pb * R * S, 4 * R * S, 4 * (max_segs + 1)]
+             4 * R * S, R * S, pb * R * S, 4 * R * S, 4 * (max_segs + 1), 8 * R * S if labels else 0]
     offs_b = [0]
     for n_b in sizes:
         offs_b.append(offs_b[-1] + -(-n_b // 16) * 16)
@@ -765,6 +806,7 @@ def pack_tokens_device(tokens: torch.Tensor, offsets: torch.Tensor, seq_len: int
     pos = reg[7].view(position_dtype).view(R, S)
     seg = reg[8].view(torch.int32).view(R, S)
     cu = reg[9].view(torch.int32)
+    lab = reg[10].view(torch.int64).view(R, S) if labels else None
     sh = _stream_handle(stream)
     h.pack_plan_device(offsets=offsets.data_ptr(), n=n, seq_len=S, max_segs=max_segs, max_rows=R,
                        seg_offsets=so.data_ptr(), row_start=rs.data_ptr(), row_end=re_.data_ptr(),
@@ -775,36 +817,45 @@ def pack_tokens_device(tokens: torch.Tensor, offsets: torch.Tensor, seq_len: int
             seg_offsets=so.data_ptr(), n_seg=0, out_tokens=out.data_ptr(), attn_mask=mask.data_ptr(),
             position_ids=pos.data_ptr(), pos_is_i64=position_dtype == torch.int64, segment_ids=seg.data_ptr(),
             cu_seqlens_out=cu.data_ptr(), rows=0, seq_len=S, pad_id=pad_id, mode=1, stream=sh, fill_rows=R,
-            dev_counts=counts.data_ptr(), tok16=tokens.dtype in _TOK16)
+            dev_counts=counts.data_ptr(), tok16=tokens.dtype in _TOK16, labels=lab.data_ptr() if labels else 0,
+            ignore_index=ignore_index)
     else:  # no rows to launch over: the (empty) plan's cu_seqlens is the single 0
         cu[:1].zero_()
-    return {"input_ids": out, "attention_mask": mask, "position_ids": pos, "segment_ids": seg, "cu_seqlens": cu,
-            "counts": counts}
+    r = {"input_ids": out, "attention_mask": mask, "position_ids": pos, "segment_ids": seg, "cu_seqlens": cu,
+         "counts": counts}
+    if labels:
+        r["labels"] = lab
+    return r
 
 
 def pack_tokens(tokens: torch.Tensor, seq_offsets, seq_len: int, pad_id: int = 0, position_dtype=torch.int64,
-                stream=None):
+                stream=None, labels: bool = False, ignore_index: int = -100):
     """Pack a ragged token stream into rows of ``seq_len`` (varlen-attention layout).
 
     Returns (tokens [R,S] i32, mask [R,S] u8, position_ids [R,S], segment_ids [R,S] i32 (-1 = pad),
-    cu_seqlens [n_seg+1] i32 over the unpadded stream ``tokens[mask.bool()]``).
+    cu_seqlens [n_seg+1] i32 over the unpadded stream ``tokens[mask.bool()]``); ``labels=True`` appends the
+    next-token labels (int64 [R,S], ``ref_token_labels``), written by the same kernel.
 
     Offsets already on the tokens' GPU: the plan is built on the device (``pack_tokens_device``) and the
     one host synchronisation is the read of the row count that sizes the result. Host offsets: the host
     plan (native ``pack_plan``), uploaded with the launch.
     """
+    ignore_index = _label_args(labels, ignore_index)
     if tokens.is_cuda and torch.is_tensor(seq_offsets) and seq_offsets.device == tokens.device:
-        r = pack_tokens_device(tokens, seq_offsets.to(torch.int64), seq_len, pad_id, position_dtype, stream=stream)
+        r = pack_tokens_device(tokens, seq_offsets.to(torch.int64), seq_len, pad_id, position_dtype, stream=stream,
+                               labels=labels, ignore_index=ignore_index)
         n_rows, n_seg = (int(v) for v in r["counts"].cpu())
         if n_rows < 0:  # cannot happen within pack_capacity; kept loud
             raise RuntimeError(f"device pack plan overflowed ({n_seg} segments)")
         return (r["input_ids"][:n_rows], r["attention_mask"][:n_rows], r["position_ids"][:n_rows],
-                r["segment_ids"][:n_rows], r["cu_seqlens"][:n_seg + 1])
+                r["segment_ids"][:n_rows], r["cu_seqlens"][:n_seg + 1],
+                *((r["labels"][:n_rows],) if labels else ()))
     rs, re_, so = pack_plan(np.asarray(seq_offsets.cpu() if torch.is_tensor(seq_offsets) else seq_offsets),
                             seq_len)
     cu = torch.from_numpy(so.astype(np.int32))
     if not tokens.is_cuda:
-        return (*ref_pack_tokens(tokens, rs, re_, so, seq_len, pad_id, position_dtype), cu)
+        r = ref_pack_tokens(tokens, rs, re_, so, seq_len, pad_id, position_dtype)
+        return (*r, cu, *((ref_token_labels(r[0], r[1], r[3], ignore_index),) if labels else ()))
     dev = tokens.device
     rs_d, re_d, so_d = (torch.from_numpy(a).to(dev, non_blocking=False) for a in (rs, re_, so))
     r = len(rs)
@@ -812,13 +863,14 @@ def pack_tokens(tokens: torch.Tensor, seq_offsets, seq_len: int, pad_id: int = 0
     mask = torch.empty((r, seq_len), dtype=torch.uint8, device=dev)
     pos = torch.empty((r, seq_len), dtype=position_dtype, device=dev)
     seg = torch.empty((r, seq_len), dtype=torch.int32, device=dev)
+    lab = torch.empty((r, seq_len), dtype=torch.int64, device=dev) if labels else None
     _native.hip().pad_pack_tokens(
         tokens=tokens.data_ptr(), offsets=0, row_start=rs_d.data_ptr(), row_end=re_d.data_ptr(),
         seg_offsets=so_d.data_ptr(), n_seg=len(so) - 1, out_tokens=out.data_ptr(), attn_mask=mask.data_ptr(),
         position_ids=pos.data_ptr(), pos_is_i64=position_dtype == torch.int64, segment_ids=seg.data_ptr(),
         cu_seqlens_out=0, rows=r, seq_len=seq_len, pad_id=pad_id, mode=1, stream=_stream_handle(stream),
-        tok16=tokens.dtype in _TOK16)
-    return out, mask, pos, seg, so_d.to(torch.int32)
+        tok16=tokens.dtype in _TOK16, labels=lab.data_ptr() if labels else 0, ignore_index=ignore_index)
+    return (out, mask, pos, seg, so_d.to(torch.int32), *((lab,) if labels else ()))
 
 
 # ------------------------------------------------- tokens out of an HBM corpus
@@ -826,9 +878,10 @@ def _align16(n: int) -> int:
     return -(-int(n) // 16) * 16
 
 
-def token_output_bytes(rows: int, seq_len: int, n_seg: int | None = None, position_dtype=torch.int64) -> int:
+def token_output_bytes(rows: int, seq_len: int, n_seg: int | None = None, position_dtype=torch.int64,
+                       labels: bool = False) -> int:
     """Bytes of the one allocation that ``carve_token_outputs`` cuts a [rows, seq_len] token batch from
-    (``n_seg`` None: pad mode, no segment ids and no cu_seqlens)."""
+    (``n_seg`` None: pad mode, no segment ids and no cu_seqlens; ``labels``: with the int64 next-token labels)."""
     # per-step host code of every token path: (x + 15) & -16 is _align16(x), written out to spare the calls
     n = int(rows) * int(seq_len)
     pos_b = (8 if position_dtype == torch.int64 else 4) * n
@@ -836,15 +889,18 @@ def token_output_bytes(rows: int, seq_len: int, n_seg: int | None = None, positi
     total = ((pos_b + 15) & -16) + ids_b + ((n + 15) & -16)  # position ids, input ids, mask
     if n_seg is not None:
         total += ((4 * (n_seg + 1) + 15) & -16) + ids_b  # cu_seqlens [n_seg + 1] i32, segment ids
+    if labels:
+        total += (8 * n + 15) & -16
     return total
 
 
 def carve_token_outputs(whole: torch.Tensor, rows: int, seq_len: int, n_seg: int | None = None,
-                        position_dtype=torch.int64):
+                        position_dtype=torch.int64, labels: bool = False):
     """(input_ids, attention_mask, position_ids, segment_ids | None, cu_seqlens | None) as views of the uint8
     buffer ``whole``: position ids, cu_seqlens, input ids, segment ids, mask, every region starting 16-byte
-    aligned. The one definition of a token batch's allocation: ``collate_token_window``, the indexed ops and the
-    resident loader all carve with it."""
+    aligned. ``labels=True`` appends the labels view (int64 [rows, seq_len]) to the tuple, carved behind the
+    mask; the other views stay where they are without it. The one definition of a token batch's allocation:
+    ``collate_token_window``, the indexed ops and the resident loader all carve with it."""
     R, S = int(rows), int(seq_len)
     n = R * S
     pos_b = (8 if position_dtype == torch.int64 else 4) * n
@@ -863,6 +919,9 @@ def carve_token_outputs(whole: torch.Tensor, rows: int, seq_len: int, n_seg: int
         seg = whole[o:o + ids_b].view(torch.int32).view(R, S)
         o += ids_a
     mask = whole[o:o + n].view(R, S)
+    if labels:
+        o += (n + 15) & -16
+        return ids, mask, pos, seg, cu, whole[o:o + 8 * n].view(torch.int64).view(R, S)
     return ids, mask, pos, seg, cu
 
 
@@ -908,54 +967,64 @@ def _upload_words(words: np.ndarray, dev, stream):
 
 
 def pad_tokens_indexed(corpus: torch.Tensor, corpus_offsets, idx, seq_len: int, pad_id: int = 0,
-                       position_dtype=torch.int64, out: torch.Tensor | None = None, stream=None):
+                       position_dtype=torch.int64, out: torch.Tensor | None = None, stream=None,
+                       labels: bool = False, ignore_index: int = -100):
     """``pad_tokens`` of sequences ``idx`` of a corpus that lives in HBM, in one pass: ``corpus`` is the flat
     device tensor (int32 or 16-bit ids), sequence i = ``corpus[corpus_offsets[i]:corpus_offsets[i + 1]]``;
     ``corpus_offsets`` and ``idx`` live on the host. The gathered stream is never materialised (the
     ``pad_pack_tokens_indexed`` kernel reads every token from the corpus). Returns (tokens [B,S] i32, mask u8
     [B,S], position ids [B,S]); ``out``: a uint8 device buffer the three are carved from
-    (``token_output_bytes`` / ``carve_token_outputs``). A CPU corpus takes the reference path
-    (``ref_gather_ragged`` + ``ref_pad_tokens``)."""
+    (``token_output_bytes`` / ``carve_token_outputs``). ``labels=True`` appends the next-token labels (int64
+    [B,S], ``ref_token_labels``), written by the same kernel and carved from the same buffer. A CPU corpus takes
+    the reference path (``ref_gather_ragged`` + ``ref_pad_tokens`` + ``ref_token_labels``)."""
     flat, start, dofs = _indexed_args(corpus, corpus_offsets, idx, position_dtype)
+    ignore_index = _label_args(labels, ignore_index)
     S = int(seq_len)
     if S <= 0:
         raise ValueError("seq_len must be > 0")
     if not flat.is_cuda:
         tokens, offs = ref_gather_ragged(flat, corpus_offsets, idx)
-        return ref_pad_tokens(tokens, offs, S, pad_id, position_dtype)
+        r = ref_pad_tokens(tokens, offs, S, pad_id, position_dtype)
+        return (*r, ref_token_labels(r[0], r[1], None, ignore_index)) if labels else r
     n, dev = int(start.size), flat.device
     words = np.concatenate([start, dofs])  # one descriptor: src_start [n], offsets [n + 1]
     desc, handle, stream = _upload_words(words, dev, stream)
     with torch.cuda.stream(stream):
-        whole = _token_out_buffer(out, token_output_bytes(n, S, None, position_dtype), dev)
-    ids, mask, pos, _, _ = carve_token_outputs(whole, n, S, None, position_dtype)
+        whole = _token_out_buffer(out, token_output_bytes(n, S, None, position_dtype, labels), dev)
+    ids, mask, pos, _, _, *lab = carve_token_outputs(whole, n, S, None, position_dtype, labels)
     base = desc.data_ptr()
     _native.hip().pad_pack_tokens_indexed(
         corpus=flat.data_ptr(), corpus_elems=flat.numel(), src_start=base, seg_src=0, offsets=base + 8 * n,
         row_start=0, row_end=0, seg_offsets=0, n_seg=0, out_tokens=ids.data_ptr(), attn_mask=mask.data_ptr(),
         position_ids=pos.data_ptr(), pos_is_i64=position_dtype == torch.int64, segment_ids=0, cu_seqlens_out=0,
-        rows=n, seq_len=S, pad_id=pad_id, mode=0, stream=handle, tok16=flat.dtype in _TOK16)
-    return ids, mask, pos
+        rows=n, seq_len=S, pad_id=pad_id, mode=0, stream=handle, tok16=flat.dtype in _TOK16,
+        labels=lab[0].data_ptr() if labels else 0, ignore_index=ignore_index)
+    return (ids, mask, pos, *lab)
 
 
 def pack_tokens_indexed(corpus: torch.Tensor, corpus_offsets, idx, seq_len: int, pad_id: int = 0,
-                        position_dtype=torch.int64, fill_rows: int = 0, out: torch.Tensor | None = None, stream=None):
+                        position_dtype=torch.int64, fill_rows: int = 0, out: torch.Tensor | None = None, stream=None,
+                        labels: bool = False, ignore_index: int = -100):
     """``pack_tokens`` of sequences ``idx`` of a corpus that lives in HBM, in one pass (see
     ``pad_tokens_indexed``): the host computes the sequences' running offsets, the native ``pack_plan`` and each
     segment's corpus element, uploads them as one descriptor, and the ``pad_pack_tokens_indexed`` kernel packs
     straight out of the corpus. Returns (tokens [R,S] i32, mask [R,S] u8, position_ids [R,S], segment_ids [R,S]
     i32 (-1 = pad), cu_seqlens [n_seg+1] i32); ``fill_rows`` > packed rows: padding rows up to that count;
-    ``out``: a uint8 device buffer the five are carved from. A CPU corpus takes the reference path
-    (``ref_gather_ragged`` + ``ref_pack_plan`` + ``ref_pack_tokens``)."""
+    ``out``: a uint8 device buffer the five are carved from. ``labels=True`` appends the next-token labels (int64
+    [R,S], ``ref_token_labels``; padding rows all ``ignore_index``), written by the same kernel and carved from
+    the same buffer. A CPU corpus takes the reference path (``ref_gather_ragged`` + ``ref_pack_plan`` +
+    ``ref_pack_tokens`` + ``ref_token_labels``)."""
     flat, start, dofs = _indexed_args(corpus, corpus_offsets, idx, position_dtype)
+    ignore_index = _label_args(labels, ignore_index)
     S = int(seq_len)
     if S <= 0:
         raise ValueError("seq_len must be > 0")
     if not flat.is_cuda:
         tokens, offs = ref_gather_ragged(flat, corpus_offsets, idx)
         rs, re_, so = ref_pack_plan(offs.numpy(), S)
-        return (*ref_pack_tokens(tokens, rs, re_, so, S, pad_id, position_dtype, fill_rows=fill_rows),
-                torch.from_numpy(so.astype(np.int32)))
+        r = ref_pack_tokens(tokens, rs, re_, so, S, pad_id, position_dtype, fill_rows=fill_rows)
+        return (*r, torch.from_numpy(so.astype(np.int32)),
+                *((ref_token_labels(r[0], r[1], r[3], ignore_index),) if labels else ()))
     n, dev = int(start.size), flat.device
     lens = np.diff(dofs)
     cap = max(int(np.sum(-(-lens // S))) if n else 0, 1)  # segments (>= rows) of this batch
@@ -970,8 +1039,8 @@ def pack_tokens_indexed(corpus: torch.Tensor, corpus_offsets, idx, seq_len: int,
     R = max(int(n_rows), int(fill_rows))
     desc, handle, stream = _upload_words(words, dev, stream)
     with torch.cuda.stream(stream):
-        whole = _token_out_buffer(out, token_output_bytes(R, S, n_seg, position_dtype), dev)
-    ids, mask, pos, seg, cu = carve_token_outputs(whole, R, S, n_seg, position_dtype)
+        whole = _token_out_buffer(out, token_output_bytes(R, S, n_seg, position_dtype, labels), dev)
+    ids, mask, pos, seg, cu, *lab = carve_token_outputs(whole, R, S, n_seg, position_dtype, labels)
     base = desc.data_ptr()
     _native.hip().pad_pack_tokens_indexed(
         corpus=flat.data_ptr(), corpus_elems=flat.numel(), src_start=base, seg_src=base + 8 * o_ss, offsets=0,
@@ -979,8 +1048,8 @@ def pack_tokens_indexed(corpus: torch.Tensor, corpus_offsets, idx, seq_len: int,
         out_tokens=ids.data_ptr(), attn_mask=mask.data_ptr(), position_ids=pos.data_ptr(),
         pos_is_i64=position_dtype == torch.int64, segment_ids=seg.data_ptr(), cu_seqlens_out=cu.data_ptr(),
         rows=n_rows, seq_len=S, pad_id=pad_id, mode=1, stream=handle, fill_rows=int(fill_rows),
-        tok16=flat.dtype in _TOK16)
-    return ids, mask, pos, seg, cu
+        tok16=flat.dtype in _TOK16, labels=lab[0].data_ptr() if labels else 0, ignore_index=ignore_index)
+    return (ids, mask, pos, seg, cu, *lab)
 
 
 # ------------------------------- tokens out of an HBM corpus, planned on the device
@@ -995,30 +1064,34 @@ def device_plan_bytes(n: int, max_segs: int | None = None, max_rows: int = 0) ->
     return total
 
 
-def device_batch_bytes(rows: int, seq_len: int, max_segs: int | None = None, position_dtype=torch.int64) -> int:
+def device_batch_bytes(rows: int, seq_len: int, max_segs: int | None = None, position_dtype=torch.int64,
+                       labels: bool = False) -> int:
     """Bytes of what a device-planned batch hands to its caller: ``token_output_bytes`` (``cu_seqlens`` of
-    capacity ``max_segs`` + 1 in pack mode) and the four int64 counts behind it."""
-    return token_output_bytes(rows, seq_len, max_segs, position_dtype) + 32
+    capacity ``max_segs`` + 1 in pack mode; ``labels``: with the next-token labels) and the four int64 counts
+    behind it."""
+    return token_output_bytes(rows, seq_len, max_segs, position_dtype, labels) + 32
 
 
 def launch_device_plan(plan_ptr: int, whole: torch.Tensor, *, corpus_ptr: int, corpus_elems: int, tok16: bool,
                        corpus_offsets_ptr: int, n_corpus: int, selector: dict, n: int, seq_len: int, pad_id: int,
                        pack: bool, max_segs: int = 0, max_rows: int = 0, position_dtype=torch.int64,
-                       stream: int = 0) -> dict:
+                       stream: int = 0, labels: bool = False, ignore_index: int = -100) -> dict:
     """The launches of one device-planned batch on raw stream ``stream``: descriptor, (pack mode) plan, pack.
     ``plan_ptr``: ``device_plan_bytes`` of 16-byte aligned device memory for the plan arrays; ``whole``:
     ``device_batch_bytes`` of uint8 device memory the outputs and the counts are carved from; ``selector``: the
     ``mode / idx / base / keys / n_domain / half_bits`` of a ``RowIndex``. Nothing here allocates, copies or
-    synchronises. Returns the dict of ``pack_tokens_indexed_device`` / ``pad_tokens_indexed_device``."""
+    synchronises. Returns the dict of ``pack_tokens_indexed_device`` / ``pad_tokens_indexed_device``
+    (``labels=True``: with ``"labels"``, written by the pack launch)."""
     h = _native.hip()
     n, S, R, M = int(n), int(seq_len), int(max_rows), int(max_segs)
+    ignore_index = _label_args(labels, ignore_index)
     o_src = plan_ptr
     o_off = o_src + _align16(8 * n)
     o_end = o_off + _align16(8 * (n + 1))
     i64 = position_dtype == torch.int64
     if not pack:
-        out_b = token_output_bytes(n, S, None, position_dtype)
-        ids, mask, pos, _, _ = carve_token_outputs(whole, n, S, None, position_dtype)
+        out_b = token_output_bytes(n, S, None, position_dtype, labels)
+        ids, mask, pos, _, _, *lab = carve_token_outputs(whole, n, S, None, position_dtype, labels)
         counts = whole[out_b:out_b + 32].view(torch.int64)
         h.token_batch_descriptor(corpus_offsets=corpus_offsets_ptr, n_corpus=n_corpus, n=n, seq_len=S, max_segs=0,
                                  src_start=o_src, offsets=o_off, seg_src=0, counts=counts.data_ptr(),
@@ -1027,30 +1100,35 @@ def launch_device_plan(plan_ptr: int, whole: torch.Tensor, *, corpus_ptr: int, c
             corpus=corpus_ptr, corpus_elems=corpus_elems, src_start=o_src, seg_src=0, offsets=o_off, row_start=0,
             row_end=0, seg_offsets=0, n_seg=0, out_tokens=ids.data_ptr(), attn_mask=mask.data_ptr(),
             position_ids=pos.data_ptr(), pos_is_i64=i64, segment_ids=0, cu_seqlens_out=0, rows=n, seq_len=S,
-            pad_id=pad_id, mode=0, stream=stream, tok16=tok16)
-        return {"input_ids": ids, "attention_mask": mask, "position_ids": pos, "counts": counts}
-    o_ss = o_end
-    o_so = o_ss + _align16(8 * M)
-    o_rs = o_so + _align16(8 * (M + 1))
-    o_re = o_rs + _align16(8 * R)
-    o_scr = o_re + _align16(8 * R)
-    out_b = token_output_bytes(R, S, M, position_dtype)
-    ids, mask, pos, seg, cu = carve_token_outputs(whole, R, S, M, position_dtype)
-    counts = whole[out_b:out_b + 32].view(torch.int64)
-    c_ptr = counts.data_ptr()
-    h.token_batch_descriptor(corpus_offsets=corpus_offsets_ptr, n_corpus=n_corpus, n=n, seq_len=S, max_segs=M,
-                             src_start=o_src, offsets=o_off, seg_src=o_ss, counts=c_ptr, pad_counts=False,
-                             stream=stream, **selector)
-    h.pack_plan_device(offsets=o_off, n=n, seq_len=S, max_segs=M, max_rows=R, seg_offsets=o_so, row_start=o_rs,
-                       row_end=o_re, counts=c_ptr, scratch=o_scr, stream=stream)
-    h.pad_pack_tokens_indexed(
-        corpus=corpus_ptr, corpus_elems=corpus_elems, src_start=o_src, seg_src=o_ss, offsets=0, row_start=o_rs,
-        row_end=o_re, seg_offsets=o_so, n_seg=0, out_tokens=ids.data_ptr(), attn_mask=mask.data_ptr(),
-        position_ids=pos.data_ptr(), pos_is_i64=i64, segment_ids=seg.data_ptr(), cu_seqlens_out=cu.data_ptr(),
-        rows=0, seq_len=S, pad_id=pad_id, mode=1, stream=stream, fill_rows=R, tok16=tok16, dev_counts=c_ptr,
-        cu_cap=M)
-    return {"input_ids": ids, "attention_mask": mask, "position_ids": pos, "segment_ids": seg, "cu_seqlens": cu,
-            "counts": counts}
+            pad_id=pad_id, mode=0, stream=stream, tok16=tok16, labels=lab[0].data_ptr() if labels else 0,
+            ignore_index=ignore_index)
+        r = {"input_ids": ids, "attention_mask": mask, "position_ids": pos, "counts": counts}
+    else:
+        o_ss = o_end
+        o_so = o_ss + _align16(8 * M)
+        o_rs = o_so + _align16(8 * (M + 1))
+        o_re = o_rs + _align16(8 * R)
+        o_scr = o_re + _align16(8 * R)
+        out_b = token_output_bytes(R, S, M, position_dtype, labels)
+        ids, mask, pos, seg, cu, *lab = carve_token_outputs(whole, R, S, M, position_dtype, labels)
+        counts = whole[out_b:out_b + 32].view(torch.int64)
+        c_ptr = counts.data_ptr()
+        h.token_batch_descriptor(corpus_offsets=corpus_offsets_ptr, n_corpus=n_corpus, n=n, seq_len=S, max_segs=M,
+                                 src_start=o_src, offsets=o_off, seg_src=o_ss, counts=c_ptr, pad_counts=False,
+                                 stream=stream, **selector)
+        h.pack_plan_device(offsets=o_off, n=n, seq_len=S, max_segs=M, max_rows=R, seg_offsets=o_so, row_start=o_rs,
+                           row_end=o_re, counts=c_ptr, scratch=o_scr, stream=stream)
+        h.pad_pack_tokens_indexed(
+            corpus=corpus_ptr, corpus_elems=corpus_elems, src_start=o_src, seg_src=o_ss, offsets=0, row_start=o_rs,
+            row_end=o_re, seg_offsets=o_so, n_seg=0, out_tokens=ids.data_ptr(), attn_mask=mask.data_ptr(),
+            position_ids=pos.data_ptr(), pos_is_i64=i64, segment_ids=seg.data_ptr(), cu_seqlens_out=cu.data_ptr(),
+            rows=0, seq_len=S, pad_id=pad_id, mode=1, stream=stream, fill_rows=R, tok16=tok16, dev_counts=c_ptr,
+            cu_cap=M, labels=lab[0].data_ptr() if labels else 0, ignore_index=ignore_index)
+        r = {"input_ids": ids, "attention_mask": mask, "position_ids": pos, "segment_ids": seg, "cu_seqlens": cu,
+             "counts": counts}
+    if labels:
+        r["labels"] = lab[0]
+    return r
 
 
 def _device_plan_args(corpus, corpus_offsets, index, perm, base, count, seq_len, position_dtype):
@@ -1115,7 +1193,8 @@ def pack_tokens_indexed_device(corpus: torch.Tensor, corpus_offsets: torch.Tenso
                                index: torch.Tensor | None = None, perm: FeistelPermutation | None = None,
                                base: int = 0, count: int | None = None, seq_len: int, pad_id: int = 0,
                                position_dtype=torch.int64, max_rows: int | None = None, max_segs: int | None = None,
-                               out: torch.Tensor | None = None, stream=None) -> dict:
+                               out: torch.Tensor | None = None, stream=None, labels: bool = False,
+                               ignore_index: int = -100) -> dict:
     """``pack_tokens_indexed`` with nothing computed on the host: ``corpus`` (flat int32 / 16-bit ids) and
     ``corpus_offsets`` (int64 [n_corpus + 1]) are device tensors, and the sequences are selected as ``gather_rows``
     selects rows -- a device ``index``, or positions ``[base, base + count)`` of ``perm`` (evaluated inline by the
@@ -1129,9 +1208,12 @@ def pack_tokens_indexed_device(corpus: torch.Tensor, corpus_offsets: torch.Tenso
     ``cu_seqlens`` and ``counts`` = device int64 ``[n_rows, n_seg, n_tokens, max_seg]`` (``n_rows`` = -1 when a
     capacity was too small: every row is then padding and ``cu_seqlens`` is all zero). ``out``: a uint8 device
     buffer of ``device_plan_bytes(n, max_segs, max_rows) + device_batch_bytes(max_rows, seq_len, max_segs)``
-    bytes that everything is carved from, else one allocation. CPU tensors take the reference path
-    (``ref_gather_ragged`` + ``ref_pack_plan`` + ``ref_pack_tokens``): the same dict."""
+    bytes that everything is carved from, else one allocation. ``labels=True`` adds ``labels`` (int64, the
+    next-token labels of ``ref_token_labels``, written by the pack launch; all ``ignore_index`` for an overflowed
+    plan) and both byte counts take ``labels=True``. CPU tensors take the reference path (``ref_gather_ragged`` +
+    ``ref_pack_plan`` + ``ref_pack_tokens``): the same dict."""
     flat, offs, n = _device_plan_args(corpus, corpus_offsets, index, perm, base, count, seq_len, position_dtype)
+    ignore_index = _label_args(labels, ignore_index)
     S = int(seq_len)
     M, R = _device_plan_caps(n, flat.numel(), S, max_rows, max_segs)
     if not flat.is_cuda:
@@ -1146,52 +1228,61 @@ def pack_tokens_indexed_device(corpus: torch.Tensor, corpus_offsets: torch.Tenso
             cu[:n_seg + 1] = torch.from_numpy(so.astype(np.int32))
         max_seg = int(np.diff(so).max()) if n_seg else 0
         counts = torch.tensor([len(rs) if ok else -1, n_seg, n_tokens, max_seg], dtype=torch.int64)
-        return {"input_ids": ids, "attention_mask": mask, "position_ids": pos, "segment_ids": seg, "cu_seqlens": cu,
-                "counts": counts}
+        r = {"input_ids": ids, "attention_mask": mask, "position_ids": pos, "segment_ids": seg, "cu_seqlens": cu,
+             "counts": counts}
+        if labels:
+            r["labels"] = ref_token_labels(ids, mask, seg, ignore_index)
+        return r
     plan_b = device_plan_bytes(n, M, R)
     handle = _stream_handle(stream)
     if isinstance(stream, int):
         stream = torch.cuda.ExternalStream(stream, device=flat.device)
     with torch.cuda.stream(stream):
-        buf = _token_out_buffer(out, plan_b + device_batch_bytes(R, S, M, position_dtype), flat.device)
+        buf = _token_out_buffer(out, plan_b + device_batch_bytes(R, S, M, position_dtype, labels), flat.device)
     return launch_device_plan(
         buf.data_ptr(), buf[plan_b:], corpus_ptr=flat.data_ptr(), corpus_elems=flat.numel(),
         tok16=flat.dtype in _TOK16, corpus_offsets_ptr=offs.data_ptr(), n_corpus=offs.numel() - 1,
         selector=_index_kw(index, perm, base) if n else _index_kw(None, None, 0), n=n, seq_len=S, pad_id=pad_id,
         pack=True, max_segs=M, max_rows=R,
-        position_dtype=position_dtype, stream=handle)
+        position_dtype=position_dtype, stream=handle, labels=labels, ignore_index=ignore_index)
 
 
 def pad_tokens_indexed_device(corpus: torch.Tensor, corpus_offsets: torch.Tensor, *,
                               index: torch.Tensor | None = None, perm: FeistelPermutation | None = None,
                               base: int = 0, count: int | None = None, seq_len: int, pad_id: int = 0,
-                              position_dtype=torch.int64, out: torch.Tensor | None = None, stream=None) -> dict:
+                              position_dtype=torch.int64, out: torch.Tensor | None = None, stream=None,
+                              labels: bool = False, ignore_index: int = -100) -> dict:
     """``pad_tokens_indexed`` with nothing computed on the host (see ``pack_tokens_indexed_device``): two
     launches, ``token_batch_descriptor`` and ``pad_pack_tokens_indexed``. Returns ``input_ids``,
     ``attention_mask``, ``position_ids`` ([n, seq_len]) and ``counts`` = device int64 ``[n, 0, n_tokens,
     max_seg]`` (``n_tokens``: the tokens of the selected sequences before truncation to ``seq_len``; ``max_seg``:
-    the longest row). ``out``: ``device_plan_bytes(n) + device_batch_bytes(n, seq_len)`` bytes. CPU tensors take
-    the reference path (``ref_gather_ragged`` + ``ref_pad_tokens``)."""
+    the longest row). ``out``: ``device_plan_bytes(n) + device_batch_bytes(n, seq_len)`` bytes. ``labels=True``
+    adds ``labels`` (``ref_token_labels``), as in ``pack_tokens_indexed_device``. CPU tensors take the reference
+    path (``ref_gather_ragged`` + ``ref_pad_tokens``)."""
     flat, offs, n = _device_plan_args(corpus, corpus_offsets, index, perm, base, count, seq_len, position_dtype)
+    ignore_index = _label_args(labels, ignore_index)
     S = int(seq_len)
     if not flat.is_cuda:
         tokens, dofs = ref_gather_ragged(flat, offs, _ref_selected(offs, n, index, perm, base))
         ids, mask, pos = ref_pad_tokens(tokens, dofs, S, pad_id, position_dtype)
         lens = np.diff(dofs.numpy())
         counts = torch.tensor([n, 0, int(dofs[-1]), int(min(lens.max(), S)) if n else 0], dtype=torch.int64)
-        return {"input_ids": ids, "attention_mask": mask, "position_ids": pos, "counts": counts}
+        r = {"input_ids": ids, "attention_mask": mask, "position_ids": pos, "counts": counts}
+        if labels:
+            r["labels"] = ref_token_labels(ids, mask, None, ignore_index)
+        return r
     plan_b = device_plan_bytes(n)
     handle = _stream_handle(stream)
     if isinstance(stream, int):
         stream = torch.cuda.ExternalStream(stream, device=flat.device)
     with torch.cuda.stream(stream):
-        buf = _token_out_buffer(out, plan_b + device_batch_bytes(n, S, None, position_dtype), flat.device)
+        buf = _token_out_buffer(out, plan_b + device_batch_bytes(n, S, None, position_dtype, labels), flat.device)
     return launch_device_plan(
         buf.data_ptr(), buf[plan_b:], corpus_ptr=flat.data_ptr(), corpus_elems=flat.numel(),
         tok16=flat.dtype in _TOK16, corpus_offsets_ptr=offs.data_ptr(), n_corpus=offs.numel() - 1,
         selector=_index_kw(index, perm, base) if n else _index_kw(None, None, 0), n=n, seq_len=S, pad_id=pad_id,
         pack=False,
-        position_dtype=position_dtype, stream=handle)
+        position_dtype=position_dtype, stream=handle, labels=labels, ignore_index=ignore_index)
 
 
 # ----------------------------------------------------------------- reductions

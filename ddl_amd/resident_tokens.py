@@ -112,7 +112,7 @@ class ResidentTokenLoader(HostPlannedTokenLoader):
                  token_rows: str | None = None, pad_id: int = 0, depth: int = 2,
                  device: str | torch.device | None = None, n_epochs: int | None = None,
                  resume_state: dict | None = None, handoff: str = "device", hbm_fraction: float = 0.8,
-                 chunk_bytes: int = 256 << 20, plan: str = "host"):
+                 chunk_bytes: int = 256 << 20, plan: str = "host", labels: bool = False, ignore_index: int = -100):
         if plan not in ("host", "device"):
             raise ValueError("plan must be 'host' or 'device'")
         if token_rows is None:  # unset: the host plan sizes every batch exactly, the device plan cannot
@@ -129,7 +129,7 @@ class ResidentTokenLoader(HostPlannedTokenLoader):
         # handoff "device": batches take microseconds, not a PCIe transfer: the caller's stream waits
         super().__init__(source, global_batch, seq_len, mode, env, seed=seed, pack_order=pack_order,
                          token_rows=token_rows, pad_id=pad_id, depth=depth, device=device, n_epochs=n_epochs,
-                         resume_state=resume_state, handoff=handoff)
+                         resume_state=resume_state, handoff=handoff, labels=labels, ignore_index=ignore_index)
         lay = self.layout
         if plan == "device" and self.LB * source.max_len > 0x7FFFFFFF:  # the host plan checks every batch instead
             raise ValueError(f"{self.LB} sequences of up to {source.max_len} tokens in one batch can overflow int32 "
@@ -166,7 +166,8 @@ class ResidentTokenLoader(HostPlannedTokenLoader):
         self._offs_dev = _replica_offsets(self._replica_key, self._offs_t, self.device, self.prep_stream)
         segs = lay.max_segments if pack else None
         self._plan_bytes = device_plan_bytes(self.LB, segs, lay.max_segments if pack else 0)
-        self._batch_bytes = device_batch_bytes(lay.max_segments if pack else self.LB, self.seq_len, segs)
+        self._batch_bytes = device_batch_bytes(lay.max_segments if pack else self.LB, self.seq_len, segs,
+                                               labels=self.labels)
         self._windows = [torch.empty(self._plan_bytes, dtype=torch.uint8, device=self.device)
                          for _ in range(self.depth + 1)]
 
@@ -190,7 +191,8 @@ class ResidentTokenLoader(HostPlannedTokenLoader):
         st = self.prep_stream
         if st is None:  # the CPU twin: the op's reference path
             perm = self.order.perm(e) if self.order.shuffle else None
-            kw = dict(perm=perm, base=base, count=LB, seq_len=S, pad_id=self.pad_id)
+            kw = dict(perm=perm, base=base, count=LB, seq_len=S, pad_id=self.pad_id, labels=self.labels,
+                      ignore_index=self.ignore_index)
             if pack:
                 r = pack_tokens_indexed_device(self._toks, self._offs_t, max_rows=lay.max_segments,
                                                max_segs=lay.max_segments, **kw)
@@ -212,7 +214,8 @@ class ResidentTokenLoader(HostPlannedTokenLoader):
                     tok16=self.source.token_bytes == 2, corpus_offsets_ptr=self._offs_dev.data_ptr(),
                     n_corpus=self.source.n, selector=dict(self._selector(e), base=base), n=LB, seq_len=S,
                     pad_id=self.pad_id, pack=pack, max_segs=lay.max_segments if pack else 0,
-                    max_rows=lay.max_segments if pack else 0, stream=st.cuda_stream)
+                    max_rows=lay.max_segments if pack else 0, stream=st.cuda_stream, labels=self.labels,
+                    ignore_index=self.ignore_index)
                 if timed:
                     ev1.record(st)
                     self._kernel_evs.append((ev0, ev1))
@@ -257,9 +260,10 @@ class ResidentTokenLoader(HostPlannedTokenLoader):
             self._upload(hip, k, win)
             # one allocation for all outputs (ops.carve_token_outputs): memory of its own, so a held batch
             # survives the rings
-            whole = torch.empty(token_output_bytes(R, S, n_seg if pack else None), dtype=torch.uint8,
-                                device=self.device)
-            ids, mask, pos, seg, cu = carve_token_outputs(whole, R, S, n_seg if pack else None)
+            whole = torch.empty(token_output_bytes(R, S, n_seg if pack else None, labels=self.labels),
+                                dtype=torch.uint8, device=self.device)
+            ids, mask, pos, seg, cu, *lab = carve_token_outputs(whole, R, S, n_seg if pack else None,
+                                                                labels=self.labels)
             h = w + self._desc_bytes
             if timed:
                 ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -271,7 +275,8 @@ class ResidentTokenLoader(HostPlannedTokenLoader):
                 out_tokens=ids.data_ptr(), attn_mask=mask.data_ptr(), position_ids=pos.data_ptr(), pos_is_i64=True,
                 segment_ids=seg.data_ptr() if pack else 0, cu_seqlens_out=cu.data_ptr() if pack else 0,
                 rows=n_rows if pack else LB, seq_len=S, pad_id=self.pad_id, mode=1 if pack else 0,
-                stream=st.cuda_stream, fill_rows=fill, tok16=self.source.token_bytes == 2)
+                stream=st.cuda_stream, fill_rows=fill, tok16=self.source.token_bytes == 2,
+                labels=lab[0].data_ptr() if lab else 0, ignore_index=self.ignore_index)
             if timed:
                 ev1.record(st)
                 self._kernel_evs.append((ev0, ev1))
@@ -284,6 +289,8 @@ class ResidentTokenLoader(HostPlannedTokenLoader):
                 batch["n_rows"] = n_rows
         else:
             batch = {"input_ids": ids, "attention_mask": mask, "position_ids": pos, "n_tokens": n_tokens}
+        if lab:
+            batch["labels"] = lab[0]
         self.assemble_s += time.perf_counter() - t_host
         return batch, ev
 

@@ -25,9 +25,15 @@ from .utils import streams
 class HostPlannedTokenLoader(PrefetchedIndexedLoader):
     def __init__(self, source: SharedTokenSource, global_batch: int, seq_len: int, mode: str, env: DDLEnv | None, *,
                  seed: int, pack_order: str, token_rows: str, pad_id: int, depth: int,
-                 device: str | torch.device | None, n_epochs: int | None, resume_state: dict | None, handoff: str):
+                 device: str | torch.device | None, n_epochs: int | None, resume_state: dict | None, handoff: str,
+                 labels: bool = False, ignore_index: int = -100):
         """The construction the loaders share. The options are checked (``check_token_options``) by the subclass,
-        in front of its own rules."""
+        in front of its own rules. ``labels``: every batch gains ``"labels"``, the next-token targets
+        (``ops.ref_token_labels``) with ``ignore_index`` where there is none, written by the kernel that writes the
+        batch; nothing else of the loader (order, checkpoint, stats) depends on it."""
+        self.labels, self.ignore_index = bool(labels), int(ignore_index)
+        if self.labels and not -(1 << 31) <= self.ignore_index < (1 << 31):
+            raise ValueError(f"ignore_index={ignore_index} does not fit int32")
         self.handoff = handoff
         self.env = env or DDLEnv()
         self.W, self.rank = self.env.world_size, self.env.rank
@@ -139,7 +145,8 @@ class HostPlannedTokenLoader(PrefetchedIndexedLoader):
                                         self._toks.data_ptr(), self._offs_t.data_ptr(), self.source.n, idx,
                                         self.source.token_bytes, self._reg["tokens"][1], 2)
         return collate_token_window(win[self._desc_bytes:], self.layout, self.mode, meta, self.pad_id,
-                                    fixed_rows=self.token_rows == "fixed")
+                                    fixed_rows=self.token_rows == "fixed", labels=self.labels,
+                                    ignore_index=self.ignore_index)
 
     def __del__(self):  # pragma: no cover - best effort
         try:

@@ -38,12 +38,13 @@ class ZeroCopyTokenLoader(HostPlannedTokenLoader):
                  env: DDLEnv | None = None, *, seed: int = 0, pack_order: str = "in_order",
                  token_rows: str = "exact", pad_id: int = 0, depth: int = 2, max_blocks: int | None = None,
                  device: str | torch.device | None = None, n_epochs: int | None = None,
-                 resume_state: dict | None = None, prefault: bool = True, handoff: str = "host"):
+                 resume_state: dict | None = None, prefault: bool = True, handoff: str = "host",
+                 labels: bool = False, ignore_index: int = -100):
         check_token_options(mode, pack_order, token_rows, handoff)
         # handoff "host": PCIe-paced batches, no barrier packet in the caller's queue (ZeroCopyLoader)
         super().__init__(source, global_batch, seq_len, mode, env, seed=seed, pack_order=pack_order,
                          token_rows=token_rows, pad_id=pad_id, depth=depth, device=device, n_epochs=n_epochs,
-                         resume_state=resume_state, handoff=handoff)
+                         resume_state=resume_state, handoff=handoff, labels=labels, ignore_index=ignore_index)
         if max_blocks is None:
             # The image loader's same-width cap of 32 workgroups (ZeroCopyLoader) was the starting point, carried
             # over, not measured for this kernel. This kernel's own sweep says uncapped: where the gather is the
@@ -80,7 +81,8 @@ class ZeroCopyTokenLoader(HostPlannedTokenLoader):
                               dst_offsets=w + self._desc_bytes + self._reg["offsets"][0], tile_start=w + 8 * LB,
                               n=LB, n_tiles=n_tiles, elem_bytes=tb, max_blocks=self.max_blocks, stream=st.cuda_stream)
             batch = collate_token_window(win[self._desc_bytes:], self.layout, self.mode, meta, self.pad_id,
-                                         fixed_rows=self.token_rows == "fixed")
+                                         fixed_rows=self.token_rows == "fixed", labels=self.labels,
+                                         ignore_index=self.ignore_index)
             ev = torch.cuda.Event()
             ev.record(st)
         return batch, ev

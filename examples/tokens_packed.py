@@ -32,6 +32,10 @@ checkpoint. ``DDL_DEVICE=cpu`` runs it (and ``--zero-copy``) with the host twin.
 only issues launches. Packing is in-order, shapes are static (fixed rows, ``cu_seqlens`` of fixed capacity) and
 ``n_tokens`` / ``n_rows`` / ``n_seg`` are 0-d device tensors; ``max_seqlen`` is an upper bound.
 
+``--labels`` (with ``--resident`` or ``--zero-copy``) asks the loader for the next-token targets as well
+(``labels=True``: int64 ``labels``, ``-100`` where a position has no target -- the end of a row or of a segment,
+padding) and trains a toy embedding + linear model on every batch with ``cross_entropy(ignore_index=-100)``.
+
 ``state_dict()`` is the indexed-kind cursor (seed, epoch, global batch), so a
 job can resume at another world size.
 """
@@ -60,15 +64,25 @@ def main() -> None:
     ap.add_argument("--device-plan", action="store_true",
                     help="with --resident: the batch's order and pack plan are built on the GPU too (in-order "
                          "packing, static shapes, counts as device scalars)")
+    ap.add_argument("--labels", action="store_true",
+                    help="with --resident or --zero-copy: the loader also delivers next-token labels, and every "
+                         "batch runs a tiny embedding -> linear -> cross_entropy step on them")
+    ap.add_argument("--vocab", type=int, default=None,
+                    help="vocabulary of the synthetic corpus (default 50257; 512 with --labels, whose toy model "
+                         "holds [positions, vocab] logits)")
     a = ap.parse_args()
     if a.zero_copy and a.resident:
         ap.error("--zero-copy and --resident are two loaders: pick one")
     if a.device_plan and not a.resident:
         ap.error("--device-plan is a mode of --resident")
+    if a.labels and not (a.zero_copy or a.resident):
+        ap.error("--labels needs --resident or --zero-copy (the producer path does not deliver labels)")
+    vocab = a.vocab or (512 if a.labels else 50257)
+    lab_kw = dict(labels=True, ignore_index=-100) if a.labels else {}
 
     name = f"ddl_amd_example_tok_{os.environ.get('MASTER_PORT', os.getpid())}"
     creator = int(os.environ.get("LOCAL_RANK", "0")) == 0
-    src = SharedTokenSource.synthetic(name, a.n_seqs, 64, a.seq_len, seed=0) if creator else None
+    src = SharedTokenSource.synthetic(name, a.n_seqs, 64, a.seq_len, vocab=vocab, seed=0) if creator else None
     try:
         with ddl_amd.start(n_producers=0 if (a.zero_copy or a.resident) else 2) as (env, conn):
             if env.world_size > 1:
@@ -82,24 +96,38 @@ def main() -> None:
             pack_order = "ffd" if a.mode == "pack" else "in_order"
             if a.resident and a.device_plan:  # first-fit-decreasing is a host plan
                 dl = ddl_amd.ResidentTokenLoader(src, a.global_batch, a.seq_len, a.mode, env, n_epochs=a.epochs,
-                                                 plan="device")
+                                                 plan="device", **lab_kw)
             elif a.resident:
                 dl = ddl_amd.ResidentTokenLoader(src, a.global_batch, a.seq_len, a.mode, env, pack_order=pack_order,
-                                                 n_epochs=a.epochs)
+                                                 n_epochs=a.epochs, **lab_kw)
             elif a.zero_copy:
                 dl = ddl_amd.ZeroCopyTokenLoader(src, a.global_batch, a.seq_len, a.mode, env, pack_order=pack_order,
-                                                 n_epochs=a.epochs)
+                                                 n_epochs=a.epochs, **lab_kw)
             else:
                 producer = TokenBatchProducer(src, a.global_batch, a.seq_len, a.mode, pack_order=pack_order,
                                               batches_per_window=a.batches_per_window)
                 dl = ddl_amd.DistributedDataLoader(producer, a.global_batch // env.world_size, conn, a.epochs,
                                                    env=env, order=ddl_amd.OrderSpec(mode="indexed"),
                                                    output=ddl_amd.OutputSpec(collate="tokens"), auto_mark=True)
+            if a.labels:  # a toy causal-LM step: the loader's labels are what cross_entropy takes, as they come
+                torch.manual_seed(0)
+                model = torch.nn.Sequential(torch.nn.Embedding(vocab, 32), torch.nn.Linear(32, vocab)).to(dl.device)
+                opt = torch.optim.SGD(model.parameters(), lr=0.1)
             for epoch in range(a.epochs):
                 real = rows = 0
                 for b in dl:
                     real += int(b["attention_mask"].sum())
                     rows += int(b.get("n_rows", b["input_ids"].shape[0]))  # fixed rows: the packed ones
+                    if a.labels:
+                        logits = model(b["input_ids"])
+                        loss = torch.nn.functional.cross_entropy(logits.view(-1, vocab), b["labels"].view(-1),
+                                                                 ignore_index=-100)
+                        opt.zero_grad(set_to_none=True)
+                        loss.backward()
+                        opt.step()
+                if a.labels and env.rank == 0:
+                    print(f"epoch {epoch}: loss {loss.item():.4f} over "
+                          f"{int((b['labels'] != -100).sum())} targets of the last batch", flush=True)
                 if env.rank == 0:
                     # cu_seqlens has one entry per SEGMENT: over-long sequences are split into seq_len chunks
                     # and empty sequences have none, so this is not the sequence count
