@@ -56,6 +56,9 @@ def main(argv=None):
                     help="resident: where a batch's order and pack plan are built. device: descriptor, plan and pack "
                          "are launches, with no host planning (in-order packing, fixed rows; the batch's counts "
                          "are device scalars)")
+    ap.add_argument("--stream", action="store_true",
+                    help="resident: the token stream format (ResidentTokenStreamLoader): --batch counts ROWS per rank "
+                         "per step, cut from the concatenated shuffled documents; table, plan and pack are launches")
     ap.add_argument("--max-blocks", type=int, default=None,
                     help="zerocopy: grid cap of the gather kernel (0 = uncapped; default: the loader's)")
     ap.add_argument("--labels", action="store_true",
@@ -68,6 +71,8 @@ def main(argv=None):
         ap.error("--labels needs --path resident or zerocopy (the producer path has no labels output)")
     if a.plan != "host" and not resident:
         ap.error("--plan device needs --path resident")
+    if a.stream and (not resident or a.plan != "host" or a.mode != "pack"):
+        ap.error("--stream needs --path resident, and is neither --plan device nor --mode pad")
     if a.plan == "device" and a.mode == "pack":
         if a.pack_order != "in_order":
             ap.error("--plan device builds the in-order plan: pass --pack-order in_order")
@@ -114,7 +119,10 @@ def main(argv=None):
                 source = src
             n_epochs = (a.warmup + a.steps + a.idle_steps + a.warmup // 2) // (a.n_seqs // gb) + 2
             pack_order = a.pack_order if a.mode == "pack" else "in_order"
-            if resident:
+            if a.stream:
+                dl = ddl_amd.ResidentTokenStreamLoader(source, gb, a.seq_len, env, labels=a.labels)
+                dl.profile_every = a.kernel_sample
+            elif resident:
                 dl = ddl_amd.ResidentTokenLoader(source, gb, a.seq_len, a.mode, env, pack_order=pack_order,
                                                  token_rows=a.token_rows, n_epochs=n_epochs, plan=a.plan,
                                                  labels=a.labels)
@@ -153,11 +161,12 @@ def main(argv=None):
             if env.world_size > 1:
                 dist.barrier(group=env.control_group)
             t0 = time.perf_counter()
-            rows = 0
+            rows = delivered = 0
             dev_counts = None  # plan="device": the counts are device scalars, summed there and read once
             for _ in range(a.steps):
                 b = next(it)
                 acc.add(b["input_ids"])
+                delivered += b["input_ids"].numel()  # positions written and handed over, padding included
                 if torch.is_tensor(b["n_tokens"]):
                     if dev_counts is None:
                         dev_counts = torch.zeros(2, dtype=torch.int64, device=b["n_tokens"].device)
@@ -216,6 +225,10 @@ def main(argv=None):
                 dist.all_reduce(t, group=env.control_group)
                 real_tokens = float(t.item())
             bpw = None if zc else dl.batches_per_window[0]
+            if env.world_size > 1:
+                t = torch.tensor([delivered], dtype=torch.float64)
+                dist.all_reduce(t, group=env.control_group)
+                delivered = float(t.item())
             dl.close()
             if env.rank == 0:
                 if resident:
@@ -224,7 +237,10 @@ def main(argv=None):
                                 "kernel_us": None if timing["kernel_us"] is None else round(timing["kernel_us"], 1),
                                 "kernel_samples": timing["kernel_samples"],
                                 "load_s": round(st["load_s"], 3), "load_gbps": round(st["load_gbps"], 2),
-                                "replica_shared": st["replica_shared"], "plan": a.plan}
+                                "replica_shared": st["replica_shared"], "plan": "stream" if a.stream else a.plan}
+                    if a.stream:
+                        per_path.update(format="stream", max_segments=st["max_segments"],
+                                        tables_built=st["tables_built"])
                 elif zc:
                     per_path = {"path": "zerocopy", "max_blocks": st["max_blocks"], "host_waits": st["host_waits"],
                                 "prefault_s": round(st["prefault_s"], 3)}
@@ -243,6 +259,8 @@ def main(argv=None):
                 res = {
                     "metric": "tokens/s fed to GPU (seq_len 4096, on-device pad/pack)", "mode": a.mode,
                     "value": round(real_tokens / dt, 1), "unit": "tokens/s (real tokens delivered)",
+                    "delivered_tokens_per_s": round(delivered / dt, 1),
+                    "delivered_density": round(real_tokens / max(delivered, 1), 4),
                     "value_est_from_mean_len": round(est_tokens / dt, 1),
                     "sequences_per_s": round(a.steps * a.batch * env.world_size / dt, 1),
                     "packed_rows_per_step": round(rows / a.steps, 2),

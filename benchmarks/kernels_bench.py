@@ -538,7 +538,121 @@ def token_labels(dev, repeats=5) -> None:
            for kind, mode in variants}}), flush=True)
 
 
+def token_stream(dev, repeats=5) -> None:
+    """The token stream kernels. (1) ``token_stream_table`` (three launches, the Feistel order inline) at the
+    ``bench_tokens.py`` corpus's document count and at 2^24 documents, against the torch composition of the same
+    scan -- ``index_select`` of the lengths by a precomputed device index, then ``cumsum`` -- which needs that
+    n-sized index built and uploaded per epoch (not timed here). (2) ``token_stream_plan`` at 64 and 2048 rows of
+    4096 tokens over the ``tokens_plan`` corpus (131072 documents), against ``token_batch_descriptor`` +
+    ``pack_plan_device`` at 64 and 2048 sequences, and the whole two-launch stream route (plan + pack). 4 windows
+    issued round-robin at launcher level: device times."""
+    from ddl_amd import _native
+    from ddl_amd.ops.kernels import (_align16, _index_kw, device_plan_bytes, launch_stream_plan,
+                                     stream_max_segments, token_stream_bytes)
+
+    hip = _native.hip()
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    rng = np.random.default_rng(0)
+    for n in (8192, 1 << 24):
+        lens = rng.integers(256, 4097, size=n)
+        offs = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+        coffs = torch.from_numpy(offs).to(dev)
+        perm = FeistelPermutation(n, 3, 1)
+        idx = torch.from_numpy(perm(np.arange(n, dtype=np.int64))).to(dev)
+        lens_dev = torch.from_numpy(lens.astype(np.int64)).to(dev)
+        table = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        scratch = torch.empty(hip.token_stream_table_scratch(n), dtype=torch.int64, device=dev)
+        sel = _index_kw(None, perm, 0)
+
+        def kernel():
+            hip.token_stream_table(corpus_offsets=coffs.data_ptr(), n_corpus=n, n=n, table=table.data_ptr(),
+                                   tile_sums=scratch.data_ptr(), stream=stream, **sel)
+
+        def composed():
+            return torch.cumsum(lens_dev.index_select(0, idx), 0)
+
+        kernel()
+        assert torch.equal(table[1:], composed()), "table and torch composition differ"
+        runs = [{"kernel": bench(kernel, reps=20), "torch": bench(composed, reps=20)} for _ in range(repeats)]
+        med = {k: float(np.median([t[k] for t in runs])) for k in runs[0]}
+        print(json.dumps({"kernel": "token_stream_table", "documents": n, "repeats": repeats,
+                          "kernel_us_median": round(med["kernel"] * 1e6, 2),
+                          "kernel_us_min_max": [round(min(t["kernel"] for t in runs) * 1e6, 2),
+                                                round(max(t["kernel"] for t in runs) * 1e6, 2)],
+                          "torch_index_select_cumsum_us_median": round(med["torch"] * 1e6, 2),
+                          "torch_us_min_max": [round(min(t["torch"] for t in runs) * 1e6, 2),
+                                               round(max(t["torch"] for t in runs) * 1e6, 2)],
+                          "kernel_over_torch": round(med["kernel"] / med["torch"], 3)}), flush=True)
+        del coffs, idx, lens_dev, table, scratch
+
+    n_src, S, rot = 131072, 4096, 4
+    lens = rng.integers(256, 4097, size=n_src)
+    offs = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    corpus = torch.randint(0, 32768, (int(offs[-1]),), dtype=torch.int16, device=dev)
+    coffs = torch.from_numpy(offs).to(dev)
+    perm = FeistelPermutation(n_src, 3, 1)
+    sel = _index_kw(None, perm, 0)
+    table = ops.token_stream_table(coffs, perm)
+    for B in (64, 2048):
+        M = stream_max_segments(lens, B, S)
+        plan_b, batch_b = token_stream_bytes(B, S, M)
+        plans = [torch.empty(plan_b, dtype=torch.uint8, device=dev) for _ in range(rot)]
+        wholes = [torch.empty(batch_b, dtype=torch.uint8, device=dev) for _ in range(rot)]
+
+        def route(k):
+            return launch_stream_plan(plans[k].data_ptr(), wholes[k], corpus_ptr=corpus.data_ptr(),
+                                      corpus_elems=corpus.numel(), tok16=True, corpus_offsets_ptr=coffs.data_ptr(),
+                                      n_corpus=n_src, table_ptr=table.data_ptr(), selector=sel, row_base=(3 + k) * B,
+                                      rows=B, seq_len=S, pad_id=0, max_segs=M, stream=stream)
+
+        def plan_only(k):
+            p = plans[k].data_ptr()
+            o_so = p + _align16(8 * M)
+            o_rs = o_so + _align16(8 * (M + 1))
+            hip.token_stream_plan(table=table.data_ptr(), corpus_offsets=coffs.data_ptr(), n_corpus=n_src, n=n_src,
+                                  row_base=(3 + k) * B, rows=B, seq_len=S, max_segs=M, seg_offsets=o_so, seg_src=p,
+                                  row_start=o_rs, row_end=o_rs + _align16(8 * B),
+                                  counts=wholes[k][batch_b - 32:].data_ptr(), stream=stream, **sel)
+
+        # the sequence-batched plan at the same step size: descriptor + in-order pack plan of B sequences
+        dplans = [torch.empty(device_plan_bytes(B, B, B), dtype=torch.uint8, device=dev) for _ in range(rot)]
+        dcounts = torch.empty(4 * rot, dtype=torch.int64, device=dev)
+
+        def seq_plan(k):
+            p = dplans[k].data_ptr()
+            o_off = p + _align16(8 * B)
+            o_ss = o_off + _align16(8 * (B + 1))
+            o_so = o_ss + _align16(8 * B)
+            o_rs = o_so + _align16(8 * (B + 1))
+            o_re = o_rs + _align16(8 * B)
+            cp = dcounts.data_ptr() + 32 * k
+            hip.token_batch_descriptor(corpus_offsets=coffs.data_ptr(), n_corpus=n_src, n=B, seq_len=S, max_segs=B,
+                                       src_start=p, offsets=o_off, seg_src=o_ss, counts=cp, pad_counts=False,
+                                       stream=stream, **_index_kw(None, perm, (3 + k) * B))
+            hip.pack_plan_device(offsets=o_off, n=B, seq_len=S, max_segs=B, max_rows=B, seg_offsets=o_so,
+                                 row_start=o_rs, row_end=o_re, counts=cp, scratch=o_re + _align16(8 * B),
+                                 stream=stream)
+
+        r = route(0)
+        torch.cuda.synchronize()
+        assert r["counts"].tolist()[::2] == [B, B * S] and bool(r["attention_mask"].all()), "stream batch not dense"
+        runs = [{"stream_plan": rotating([lambda k=k: plan_only(k) for k in range(rot)]),
+                 "descriptor_plus_pack_plan": rotating([lambda k=k: seq_plan(k) for k in range(rot)]),
+                 "stream_route": rotating([lambda k=k: route(k) for k in range(rot)])} for _ in range(repeats)]
+        med = {k: float(np.median([t[k] for t in runs])) for k in runs[0]}
+        print(json.dumps({
+            "kernel": "token_stream_plan", "rows": B, "seq_len": S, "documents": n_src, "max_segs": M,
+            "segments": int(r["counts"][1]), "repeats": repeats,
+            **{k + "_us_median": round(v * 1e6, 2) for k, v in med.items()},
+            **{k + "_us_min_max": [round(min(t[k] for t in runs) * 1e6, 2), round(max(t[k] for t in runs) * 1e6, 2)]
+               for k in med},
+            "stream_route_tokens_per_s": round(B * S / med["stream_route"], 1)}), flush=True)
+
+
 if __name__ == "__main__":
+    if "--only-token-stream" in sys.argv[1:]:  # profiles/token_stream/
+        token_stream(torch.device("cuda", 0))
+        sys.exit(0)
     if "--only-token-labels" in sys.argv[1:]:  # profiles/token_labels/
         token_labels(torch.device("cuda", 0))
         sys.exit(0)

@@ -800,6 +800,50 @@ PYBIND11_MODULE(_ddl_hip, m) {
       py::arg("n_domain"), py::arg("half_bits"), py::arg("n"), py::arg("seq_len"), py::arg("max_segs"),
       py::arg("src_start"), py::arg("offsets"), py::arg("seg_src"), py::arg("counts"), py::arg("pad_counts"),
       py::arg("stream"));
+  m.def("token_stream_table_scratch", &ddl::token_stream_table_scratch, py::arg("n"));
+  m.def(
+      "token_stream_table",
+      [](uintptr_t corpus_offsets, int64_t n_corpus, int mode, uintptr_t idx, int64_t base, std::vector<uint64_t> keys,
+         uint64_t n_domain, uint32_t half_bits, int64_t n, uintptr_t table, uintptr_t tile_sums, uintptr_t stream) {
+        ddl::StreamTableSpec sp{};
+        sp.corpus_offsets = as_ptr<const int64_t>(corpus_offsets);
+        sp.n_corpus = n_corpus;
+        sp.ri = make_index(mode, idx, base, keys, n_domain, half_bits);
+        sp.n = n;
+        sp.table = as_ptr<int64_t>(table);
+        sp.tile_sums = as_ptr<int64_t>(tile_sums);
+        check_rc(ddl::token_stream_table(sp, as_stream(stream)), "token_stream_table");
+      },
+      py::arg("corpus_offsets"), py::arg("n_corpus"), py::arg("mode"), py::arg("idx"), py::arg("base"), py::arg("keys"),
+      py::arg("n_domain"), py::arg("half_bits"), py::arg("n"), py::arg("table"), py::arg("tile_sums"),
+      py::arg("stream"));
+  m.def(
+      "token_stream_plan",
+      [](uintptr_t table, uintptr_t corpus_offsets, int64_t n_corpus, int mode, uintptr_t idx, int64_t base,
+         std::vector<uint64_t> keys, uint64_t n_domain, uint32_t half_bits, int64_t n, int64_t row_base, int64_t rows,
+         int64_t seq_len, int64_t max_segs, uintptr_t seg_offsets, uintptr_t seg_src, uintptr_t row_start,
+         uintptr_t row_end, uintptr_t counts, uintptr_t stream) {
+        ddl::StreamPlanSpec sp{};
+        sp.table = as_ptr<const int64_t>(table);
+        sp.corpus_offsets = as_ptr<const int64_t>(corpus_offsets);
+        sp.n_corpus = n_corpus;
+        sp.ri = make_index(mode, idx, base, keys, n_domain, half_bits);
+        sp.n = n;
+        sp.row_base = row_base;
+        sp.rows = rows;
+        sp.seq_len = seq_len;
+        sp.max_segs = max_segs;
+        sp.seg_offsets = as_ptr<int64_t>(seg_offsets);
+        sp.seg_src = as_ptr<int64_t>(seg_src);
+        sp.row_start = as_ptr<int64_t>(row_start);
+        sp.row_end = as_ptr<int64_t>(row_end);
+        sp.counts = as_ptr<int64_t>(counts);
+        check_rc(ddl::token_stream_plan(sp, as_stream(stream)), "token_stream_plan");
+      },
+      py::arg("table"), py::arg("corpus_offsets"), py::arg("n_corpus"), py::arg("mode"), py::arg("idx"),
+      py::arg("base"), py::arg("keys"), py::arg("n_domain"), py::arg("half_bits"), py::arg("n"), py::arg("row_base"),
+      py::arg("rows"), py::arg("seq_len"), py::arg("max_segs"), py::arg("seg_offsets"), py::arg("seg_src"),
+      py::arg("row_start"), py::arg("row_end"), py::arg("counts"), py::arg("stream"));
   m.attr("TOKEN_SEG_LDS_CAP") = ddl::kTiSegCap;
   m.attr("RAGGED_MAP_CAP") = ddl::kRaggedMapCap;
   m.def(

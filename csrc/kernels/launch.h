@@ -176,6 +176,48 @@ struct BatchDescSpec {
 };
 int token_batch_descriptor(const BatchDescSpec& spec, hipStream_t st);
 
+// tokens_stream.hip ---------------------------------------------------------
+// The token stream of an epoch: concat(document q_0 .. q_{n-1}), q_k = source_row(ri, k) (the Feistel order of
+// the epoch, an explicit device index, or the identity), cut into rows of seq_len tokens.
+// token_stream_table: table[i] = the tokens in front of document i, i = 0 .. n (table[n] = the stream's length):
+// a device-wide exclusive scan, three launches on `st` (tile sums, the scan of the tile sums by one workgroup,
+// the tiles' scans), no atomics and no waiting between workgroups. tile_sums: token_stream_table_scratch(n)
+// int64 of device scratch. An index outside [0, n_corpus) is an empty document.
+struct StreamTableSpec {
+  const int64_t* corpus_offsets;  // [n_corpus + 1], device
+  int64_t n_corpus;
+  RowIndex ri;
+  int64_t n;          // documents of the order
+  int64_t* table;     // out: [n + 1]
+  int64_t* tile_sums; // scratch
+};
+int64_t token_stream_table_scratch(int64_t n);
+int token_stream_table(const StreamTableSpec& spec, hipStream_t st);
+// token_stream_plan (one workgroup): the pack plan of rows [row_base, row_base + rows) of the stream, i.e. of
+// the window [T0, T1) = [row_base * seq_len, min((row_base + rows) * seq_len, table[n])), as
+// pad_pack_tokens_indexed takes it in pack mode with dev_counts = counts, fill_rows = rows, cu_cap = max_segs. A
+// segment is a maximal run of one document inside one row: seg_offsets[k] = its start - T0 (entry n_seg = the
+// window's tokens), seg_src[k] = the corpus element of its first token; row_start / row_end [rows] = the rows'
+// limits clamped to the window's tokens; counts = {rows holding a token, n_seg, tokens, longest segment}, counts[0]
+// = -1 when n_seg > max_segs (nothing is written past the capacity; pad_pack_tokens_indexed then writes padding).
+struct StreamPlanSpec {
+  const int64_t* table;           // [n + 1], token_stream_table of the same ri and n
+  const int64_t* corpus_offsets;  // [n_corpus + 1], device
+  int64_t n_corpus;
+  RowIndex ri;
+  int64_t n;
+  int64_t row_base;
+  int64_t rows;
+  int64_t seq_len;
+  int64_t max_segs;      // seg_offsets holds max_segs + 1 entries, seg_src max_segs
+  int64_t* seg_offsets;  // out
+  int64_t* seg_src;      // out
+  int64_t* row_start;    // out: [rows]
+  int64_t* row_end;      // out: [rows]
+  int64_t* counts;       // out: [4]
+};
+int token_stream_plan(const StreamPlanSpec& spec, hipStream_t st);
+
 // ragged.hip ----------------------------------------------------------------
 // Device twin of the host gather_ragged: sequence i (src_start[i] elements into src, dst_offsets[i + 1] -
 // dst_offsets[i] elements of elem_bytes = 2 or 4) -> dst[dst_offsets[i] ...). src: HBM or pinned,

@@ -21,6 +21,7 @@ __all__ = [
     "IndexedProducer",
     "ZeroCopyTokenLoader",
     "ResidentTokenLoader",
+    "ResidentTokenStreamLoader",
     "DataLoader",
     "OutputSpec",
     "StagingSpec",
@@ -51,6 +52,10 @@ def __getattr__(name):
         from .resident_tokens import ResidentTokenLoader
 
         return ResidentTokenLoader
+    if name == "ResidentTokenStreamLoader":
+        from .token_stream import ResidentTokenStreamLoader
+
+        return ResidentTokenStreamLoader
     if name == "DataLoader":
         from .frontend import DataLoader
 

@@ -1285,6 +1285,230 @@ def pad_tokens_indexed_device(corpus: torch.Tensor, corpus_offsets: torch.Tensor
         position_dtype=position_dtype, stream=handle, labels=labels, ignore_index=ignore_index)
 
 
+# ------------------------------------- the token stream: full [B, S] rows cut from the epoch's documents
+def _stream_order(n: int, perm) -> np.ndarray:
+    pos = np.arange(n, dtype=np.int64)
+    return pos if perm is None else np.asarray(perm(pos), dtype=np.int64)
+
+
+def _stream_lengths(offs: np.ndarray, q: np.ndarray) -> np.ndarray:
+    return np.maximum(offs[q + 1] - offs[q], 0) if q.size else np.zeros(0, dtype=np.int64)
+
+
+def _stream_default_segs(n: int, rows: int, seq_len: int) -> int:
+    """A capacity that needs no length: every document that touches a window holds one of its tokens."""
+    return max(1, min(int(n), int(rows) * int(seq_len)) + int(rows) - 1)
+
+
+def stream_max_segments(lengths, rows: int, seq_len: int) -> int:
+    """The most segments a ``rows x seq_len`` window of the token stream can hold, in any document order: with
+    ``k`` = the largest count of smallest non-empty lengths whose sum is ``<= rows * seq_len``, at most ``k`` + 2
+    documents touch a window (``k`` inside it, one cut at either end), and each of the ``rows`` - 1 interior row
+    boundaries splits at most one of them: ``min(k + 2, n_nonempty) + rows - 1`` (at least 1)."""
+    lens = np.asarray(lengths, dtype=np.int64).reshape(-1)
+    lens = np.sort(lens[lens > 0])
+    k = int(np.searchsorted(np.cumsum(lens), int(rows) * int(seq_len), side="right"))
+    return max(1, min(k + 2, int(lens.size)) + int(rows) - 1)
+
+
+def ref_stream_tokens(corpus: torch.Tensor, corpus_offsets, *, perm=None, row_base: int, rows: int, seq_len: int,
+                      pad_id: int = 0, position_dtype=torch.int64, max_segs: int | None = None, labels: bool = False,
+                      ignore_index: int = -100) -> dict:
+    """The definition of the token stream format, in NumPy on the CPU (no plan code is involved)::
+
+        stream = concat(corpus[offs[q_i] : offs[q_i + 1]] for i in range(n)),  q_i = perm(i) (or i),  T = len(stream)
+        row r  = stream[(row_base + r) * S : (row_base + r + 1) * S]
+
+    Documents carry their own EOS: nothing is inserted. Positions at or past ``T`` are padding (``pad_id``, mask
+    0, position 0, segment -1). A segment is a maximal run of one document inside one row, numbered in row-major
+    order across the batch (an empty document makes none); ``position_ids`` restart at 0 in every segment, also
+    where a document continues from the previous row -- the rule the pack mode applies to the chunks of an
+    over-long sequence. Returns ``input_ids``, ``attention_mask``, ``position_ids``, ``segment_ids`` ([rows, S]),
+    ``cu_seqlens`` (int32 [max_segs + 1]: the batch-local segment starts, entries past ``n_seg`` = the batch's
+    token count) and ``counts`` = int64 ``[n_rows, n_seg, n_tokens, max_seg]`` (``n_rows``: the rows holding a
+    token); ``labels=True`` adds ``labels`` = ``ref_token_labels`` of the batch. ``n_seg > max_segs`` is an
+    overflow: ``n_rows`` = -1, every row padding, ``cu_seqlens`` all zero, labels all ``ignore_index``.
+    ``max_segs`` None: ``min(n, rows * S) + rows - 1``, which no window exceeds."""
+    S, R, base = int(seq_len), int(rows), int(row_base)
+    if S <= 0 or R < 1 or base < 0:
+        raise ValueError("seq_len must be > 0, rows >= 1 and row_base >= 0")
+    offs = torch.as_tensor(corpus_offsets).to("cpu", torch.int64).reshape(-1).numpy()
+    n = offs.size - 1
+    q = _stream_order(n, perm)
+    lens = _stream_lengths(offs, q)
+    table = np.concatenate([np.zeros(1, dtype=np.int64), np.cumsum(lens, dtype=np.int64)])
+    M = _stream_default_segs(n, R, S) if max_segs is None else int(max_segs)
+    g = base * S + np.arange(R * S, dtype=np.int64)
+    n_tok = int(np.count_nonzero(g < table[-1]))  # the valid positions are a prefix of the batch
+    gv = g[:n_tok]
+    d = np.searchsorted(table, gv, side="right") - 1  # the last document starting at or before g: never an empty one
+    new = np.ones(n_tok, dtype=bool)
+    new[1:] = (d[1:] != d[:-1]) | (gv[1:] % S == 0)
+    starts = np.flatnonzero(new)
+    n_seg = int(starts.size)
+    seg = np.cumsum(new) - 1
+    local = np.arange(n_tok, dtype=np.int64)
+    ok = n_seg <= M
+    ids = np.full(R * S, int(pad_id), dtype=np.int32)
+    mask = np.zeros(R * S, dtype=np.uint8)
+    pos = np.zeros(R * S, dtype=np.int64)
+    sid = np.full(R * S, -1, dtype=np.int32)
+    cu = np.zeros(M + 1, dtype=np.int32)
+    if ok and n_tok:
+        flat = widen_tokens(corpus.cpu().reshape(-1)).numpy()
+        ids[:n_tok] = flat[offs[q[d]] + (gv - table[d])]
+        mask[:n_tok] = 1
+        pos[:n_tok] = local - starts[seg]
+        sid[:n_tok] = seg
+    if ok:
+        cu[:n_seg] = starts
+        cu[n_seg:] = n_tok
+    max_seg = int(np.diff(np.append(starts, n_tok)).max()) if n_seg else 0
+    counts = torch.tensor([-(-n_tok // S) if ok else -1, n_seg, n_tok, max_seg], dtype=torch.int64)
+    r = {"input_ids": torch.from_numpy(ids).view(R, S), "attention_mask": torch.from_numpy(mask).view(R, S),
+         "position_ids": torch.from_numpy(pos).to(position_dtype).view(R, S),
+         "segment_ids": torch.from_numpy(sid).view(R, S), "cu_seqlens": torch.from_numpy(cu), "counts": counts}
+    if labels:
+        r["labels"] = ref_token_labels(r["input_ids"], r["attention_mask"], r["segment_ids"], ignore_index)
+    return r
+
+
+def token_stream_table(corpus_offsets: torch.Tensor, perm: FeistelPermutation | None = None,
+                       out: torch.Tensor | None = None, stream=None, scratch: torch.Tensor | None = None):
+    """``table`` (int64 [n + 1]) of the token stream of an epoch: ``table[i]`` = the tokens in front of document
+    ``i`` of the order (``perm``, or the identity), ``table[n]`` = the stream's length. Device offsets: the
+    ``token_stream_table`` kernels (a three-launch device-wide scan with the permutation evaluated inline: no
+    n-sized index, no host step); ``out``: an int64 device tensor of n + 1 entries, ``scratch``: one of
+    ``_native.hip().token_stream_table_scratch(n)``, else allocated here. CPU offsets: NumPy."""
+    if not isinstance(corpus_offsets, torch.Tensor) or corpus_offsets.dtype != torch.int64:
+        raise TypeError("corpus_offsets must be an int64 tensor")
+    offs = corpus_offsets.reshape(-1)
+    if offs.numel() < 1 or not offs.is_contiguous():
+        raise ValueError("corpus_offsets must be contiguous and hold at least one entry")
+    n = offs.numel() - 1
+    if perm is not None and perm.n != n:
+        raise IndexError("the permutation's domain is not the corpus")
+    if not offs.is_cuda:
+        o = offs.numpy()
+        t = np.concatenate([np.zeros(1, dtype=np.int64), np.cumsum(_stream_lengths(o, _stream_order(n, perm)))])
+        t = torch.from_numpy(t.astype(np.int64))
+        if out is not None:
+            out[:n + 1].copy_(t)
+            return out[:n + 1]
+        return t
+    h = _native.hip()
+    handle = _stream_handle(stream)
+    if isinstance(stream, int):
+        stream = torch.cuda.ExternalStream(stream, device=offs.device)
+    need = h.token_stream_table_scratch(n)
+    with torch.cuda.stream(stream):
+        if out is None:
+            out = torch.empty(n + 1, dtype=torch.int64, device=offs.device)
+        if scratch is None:
+            scratch = torch.empty(need, dtype=torch.int64, device=offs.device)
+    for name, t, size in (("out", out, n + 1), ("scratch", scratch, need)):
+        if t.dtype != torch.int64 or t.device != offs.device or not t.is_contiguous() or t.numel() < size:
+            raise ValueError(f"{name} must be a contiguous int64 tensor of >= {size} entries on the offsets' device")
+    h.token_stream_table(corpus_offsets=offs.data_ptr(), n_corpus=n, n=n, table=out.data_ptr(),
+                         tile_sums=scratch.data_ptr(), stream=handle,
+                         **(_index_kw(None, perm, 0) if n else _index_kw(None, None, 0)))
+    return out[:n + 1]
+
+
+def token_stream_bytes(rows: int, seq_len: int, max_segs: int, position_dtype=torch.int64,
+                       labels: bool = False) -> tuple[int, int]:
+    """(plan bytes, batch bytes) of one token stream batch. The plan -- seg_src [max_segs], seg_offsets
+    [max_segs + 1], row_start / row_end [rows] -- lives between the two launches and nothing a caller holds is
+    there; the batch is ``device_batch_bytes``: the outputs, ``cu_seqlens`` of capacity ``max_segs`` + 1 and the
+    four int64 counts."""
+    plan = _align16(8 * max_segs) + _align16(8 * (max_segs + 1)) + 2 * _align16(8 * rows)
+    return plan, device_batch_bytes(rows, seq_len, max_segs, position_dtype, labels)
+
+
+def launch_stream_plan(plan_ptr: int, whole: torch.Tensor, *, corpus_ptr: int, corpus_elems: int, tok16: bool,
+                       corpus_offsets_ptr: int, n_corpus: int, table_ptr: int, selector: dict, row_base: int,
+                       rows: int, seq_len: int, pad_id: int, max_segs: int, position_dtype=torch.int64,
+                       stream: int = 0, labels: bool = False, ignore_index: int = -100) -> dict:
+    """The two launches of one token stream batch on raw stream ``stream``: ``token_stream_plan`` and
+    ``pad_pack_tokens_indexed`` (pack mode, counts read from device memory). ``plan_ptr`` / ``whole``: the two
+    sizes of ``token_stream_bytes``, 16-byte aligned device memory; ``selector``: the ``RowIndex`` of the epoch's
+    order with base 0, the one ``table_ptr``'s table was built with. Nothing here allocates, copies or
+    synchronises. Returns the dict of ``stream_tokens_indexed_device``."""
+    h = _native.hip()
+    S, R, M = int(seq_len), int(rows), int(max_segs)
+    ignore_index = _label_args(labels, ignore_index)
+    o_ss = plan_ptr
+    o_so = o_ss + _align16(8 * M)
+    o_rs = o_so + _align16(8 * (M + 1))
+    o_re = o_rs + _align16(8 * R)
+    out_b = token_output_bytes(R, S, M, position_dtype, labels)
+    ids, mask, pos, seg, cu, *lab = carve_token_outputs(whole, R, S, M, position_dtype, labels)
+    counts = whole[out_b:out_b + 32].view(torch.int64)
+    c_ptr = counts.data_ptr()
+    h.token_stream_plan(table=table_ptr, corpus_offsets=corpus_offsets_ptr, n_corpus=n_corpus, n=n_corpus,
+                        row_base=int(row_base), rows=R, seq_len=S, max_segs=M, seg_offsets=o_so, seg_src=o_ss,
+                        row_start=o_rs, row_end=o_re, counts=c_ptr, stream=stream, **selector)
+    h.pad_pack_tokens_indexed(
+        corpus=corpus_ptr, corpus_elems=corpus_elems, src_start=0, seg_src=o_ss, offsets=0, row_start=o_rs,
+        row_end=o_re, seg_offsets=o_so, n_seg=0, out_tokens=ids.data_ptr(), attn_mask=mask.data_ptr(),
+        position_ids=pos.data_ptr(), pos_is_i64=position_dtype == torch.int64, segment_ids=seg.data_ptr(),
+        cu_seqlens_out=cu.data_ptr(), rows=0, seq_len=S, pad_id=pad_id, mode=1, stream=stream, fill_rows=R,
+        tok16=tok16, dev_counts=c_ptr, cu_cap=M, labels=lab[0].data_ptr() if labels else 0,
+        ignore_index=ignore_index)
+    r = {"input_ids": ids, "attention_mask": mask, "position_ids": pos, "segment_ids": seg, "cu_seqlens": cu,
+         "counts": counts}
+    if labels:
+        r["labels"] = lab[0]
+    return r
+
+
+def stream_tokens_indexed_device(corpus: torch.Tensor, corpus_offsets: torch.Tensor, table: torch.Tensor | None = None,
+                                 *, perm: FeistelPermutation | None = None, row_base: int, rows: int, seq_len: int,
+                                 pad_id: int = 0, max_segs: int | None = None, position_dtype=torch.int64,
+                                 labels: bool = False, ignore_index: int = -100, out: torch.Tensor | None = None,
+                                 stream=None) -> dict:
+    """Rows ``[row_base, row_base + rows)`` of the token stream (``ref_stream_tokens``, the definition) out of a
+    corpus in HBM: ``corpus`` (flat int32 / 16-bit ids), ``corpus_offsets`` (int64 [n + 1]) and ``table``
+    (``token_stream_table`` of the same ``perm``) are device tensors. Two launches -- ``token_stream_plan`` and
+    ``pad_pack_tokens_indexed`` -- no copy, no synchronisation and no allocation beyond ``out``: a uint8 device
+    buffer of ``sum(token_stream_bytes(rows, seq_len, max_segs, position_dtype, labels))`` bytes that the plan and
+    everything returned are carved from, else one allocation. The result is static-shaped ([rows, seq_len],
+    ``cu_seqlens`` of ``max_segs`` + 1 entries) and holds no padding except past the stream's end. ``max_segs``
+    None: ``min(n, rows * seq_len) + rows - 1``, safe without a length (``stream_max_segments`` of the lengths is
+    the tight one). CPU tensors take ``ref_stream_tokens`` (``table`` is not needed): the same dict."""
+    flat, offs, _ = _device_plan_args(corpus, corpus_offsets, None, None, 0, 0, seq_len, position_dtype)
+    ignore_index = _label_args(labels, ignore_index)
+    S, R, n = int(seq_len), int(rows), offs.numel() - 1
+    if R < 1 or int(row_base) < 0:
+        raise ValueError("rows must be >= 1 and row_base >= 0")
+    if R * S > 0x7FFFFFFF:
+        raise ValueError(f"{R} rows of {S} tokens overflow int32 cu_seqlens")
+    if perm is not None and perm.n != n:
+        raise IndexError("the permutation's domain is not the corpus")
+    M = _stream_default_segs(n, R, S) if max_segs is None else int(max_segs)
+    if M < 1 or M >= (1 << 31) - 1:
+        raise ValueError("max_segs must be >= 1 and fit the plan's int32 segment ids")
+    if not flat.is_cuda:
+        return ref_stream_tokens(flat, offs, perm=perm, row_base=row_base, rows=R, seq_len=S, pad_id=pad_id,
+                                 position_dtype=position_dtype, max_segs=M, labels=labels, ignore_index=ignore_index)
+    if (not isinstance(table, torch.Tensor) or table.dtype != torch.int64 or table.device != flat.device
+            or not table.is_contiguous() or table.numel() < n + 1):
+        raise ValueError("table must be a contiguous int64 tensor of n + 1 entries on the corpus's device "
+                         "(token_stream_table)")
+    plan_b, batch_b = token_stream_bytes(R, S, M, position_dtype, labels)
+    handle = _stream_handle(stream)
+    if isinstance(stream, int):
+        stream = torch.cuda.ExternalStream(stream, device=flat.device)
+    with torch.cuda.stream(stream):
+        buf = _token_out_buffer(out, plan_b + batch_b, flat.device)
+    return launch_stream_plan(
+        buf.data_ptr(), buf[plan_b:], corpus_ptr=flat.data_ptr(), corpus_elems=flat.numel(),
+        tok16=flat.dtype in _TOK16, corpus_offsets_ptr=offs.data_ptr(), n_corpus=n, table_ptr=table.data_ptr(),
+        selector=_index_kw(None, perm, 0) if n else _index_kw(None, None, 0), row_base=int(row_base), rows=R,
+        seq_len=S, pad_id=pad_id, max_segs=M, position_dtype=position_dtype, stream=handle, labels=labels,
+        ignore_index=ignore_index)
+
+
 # ----------------------------------------------------------------- reductions
 def ref_checksum(x: torch.Tensor) -> int:
     b = x.detach().contiguous().reshape(-1).view(torch.uint8).cpu().numpy()

@@ -1,0 +1,281 @@
+"""HBM-resident token stream loader: every step is ``B`` rows of exactly ``S`` tokens, cut from the
+concatenation of the epoch's shuffled documents (the GPT pre-training format of Megatron's GPT dataset and
+nanoGPT).
+
+The sequence-batched token paths deliver ``LB`` documents per step, padded or packed into however many rows
+they need; in-order packing fills about 75% of the row space. Here the epoch's token stream is
+
+    stream_e = concat(document perm_e(0), perm_e(1), ..., perm_e(n - 1))        (no separator: documents carry
+                                                                                  their own EOS)
+
+and row ``r`` of the epoch is ``stream_e[r * S : (r + 1) * S]``: 100% dense, static-shaped, and the same rows at
+every world size (rank ``r`` of ``W`` takes rows ``[g * GB + r * LB, g * GB + (r + 1) * LB)`` of global batch
+``g``). ``rows_per_epoch = T // S`` and ``batches_per_epoch = rows_per_epoch // global_batch``; the tail is
+dropped, a different one each epoch under ``shuffle``.
+
+Nothing is planned on the host. The corpus replica and its offsets are ``ResidentTokenLoader``'s (shared with
+any over the same corpus). Once per epoch the ``token_stream_table`` kernels scan the documents' lengths in the
+epoch's order (the Feistel permutation inline) into ``table [n + 1]``; per step ``token_stream_plan`` finds the
+window's documents in it and writes the pack plan -- a segment is a maximal run of one document inside one row,
+``position_ids`` restart in every segment -- which the unchanged ``pad_pack_tokens_indexed`` renders: two
+launches, no copy, no host read of device memory, no synchronisation per step or per epoch (two tables are
+kept, since prefetch crosses the epoch boundary; everything is ordered by the prep stream). ``ops.ref_stream_tokens``
+is the definition; with ``device="cpu"`` the loader runs it and gives the same dict.
+"""
+
+from __future__ import annotations
+
+import time
+
+import numpy as np
+import torch
+
+from . import _native
+from .exceptions import DDLError
+from .models.tokens import SharedTokenSource
+from .ops.kernels import launch_stream_plan, ref_stream_tokens, stream_max_segments, token_stream_bytes
+from .permutation import FeistelPermutation
+from .resident import STATE_VERSION, PrefetchedIndexedLoader
+from .resident_tokens import _REPLICAS, _acquire_replica, _release_replica, _replica_offsets
+from .types import DDLEnv
+from .utils import streams
+
+
+class _RowOrder:
+    """What ``PrefetchedIndexedLoader`` asks of an order, over the rows of the stream."""
+
+    def __init__(self, rows_per_epoch: int, global_batch: int, seed: int, shuffle: bool):
+        self.n_samples, self.global_batch, self.seed, self.shuffle = rows_per_epoch, global_batch, seed, shuffle
+        self.batches_per_epoch = rows_per_epoch // global_batch
+
+
+class ResidentTokenStreamLoader(PrefetchedIndexedLoader):
+    def __init__(self, source: SharedTokenSource, global_batch: int, seq_len: int = 4096, env: DDLEnv | None = None,
+                 *, seed: int = 0, shuffle: bool = True, pad_id: int = 0, depth: int = 2,
+                 device: str | torch.device | None = None, n_epochs: int | None = None,
+                 resume_state: dict | None = None, handoff: str = "device", hbm_fraction: float = 0.8,
+                 chunk_bytes: int = 256 << 20, max_segments: int | None = None, labels: bool = False,
+                 ignore_index: int = -100):
+        """``global_batch`` counts rows. ``max_segments``: the capacity of a batch's ``cu_seqlens`` (default
+        ``ops.stream_max_segments``, which no window of any order exceeds; a smaller one that a batch overflows
+        gives that batch as padding with ``n_rows`` = -1)."""
+        if handoff not in ("device", "host"):
+            raise ValueError("handoff must be 'device' or 'host'")
+        self.labels, self.ignore_index = bool(labels), int(ignore_index)
+        if self.labels and not -(1 << 31) <= self.ignore_index < (1 << 31):
+            raise ValueError(f"ignore_index={ignore_index} does not fit int32")
+        self.handoff = handoff
+        self.env = env or DDLEnv()
+        self.W, self.rank = self.env.world_size, self.env.rank
+        self.source, self.seq_len, self.pad_id = source, int(seq_len), int(pad_id)
+        self.GB = int(global_batch)
+        if self.seq_len <= 0 or self.GB <= 0:
+            raise ValueError("seq_len and global_batch must be positive")
+        if self.GB % self.W:
+            raise ValueError(f"global batch {self.GB} not divisible by world size {self.W}")
+        self.LB = self.GB // self.W
+        if self.LB * self.seq_len > 0x7FFFFFFF:
+            raise ValueError(f"{self.LB} rows of {self.seq_len} tokens overflow int32 cu_seqlens")
+        self._toks = source.tokens.tensor().view(-1)  # keeps the mappings alive
+        self._offs_t = source.offsets.tensor().view(-1)
+        offs = self._offs_t.numpy()
+        lens = np.maximum(np.diff(offs), 0)
+        self.n_documents, self.total_tokens = int(source.n), int(lens.sum())
+        if self.total_tokens < self.GB * self.seq_len:
+            raise ValueError(f"the corpus holds {self.total_tokens} tokens, fewer than one global batch of "
+                             f"{self.GB} x {self.seq_len}")
+        self.order = _RowOrder(self.total_tokens // self.seq_len, self.GB, int(seed), bool(shuffle))
+        self.max_segments = (stream_max_segments(lens, self.LB, self.seq_len) if max_segments is None
+                             else int(max_segments))
+        if self.max_segments < 1:
+            raise ValueError("max_segments must be >= 1")
+        self._max_seqlen = min(self.seq_len, int(source.max_len))
+        self.out_dtype = torch.int32
+        if device is None:
+            device = self.env.device or ("cuda" if torch.cuda.is_available() else "cpu")
+        self.device = torch.device(device)
+        if self.device.type == "cuda" and self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self._init_cursor(seed, depth, n_epochs, resume_state)
+        self.nbytes = int(offs[-1]) * source.token_bytes if source.n else 0
+        self.n_elems = self.nbytes // source.token_bytes
+        self.prep_stream = streams.batch_stream(self.device) if self.device.type == "cuda" else None
+        self._replica_key = None
+        self.replica_shared = False
+        self.load_s = 0.0
+        self.assemble_s = 0.0  # wall time spent in _assemble (host_us_per_step of the benchmark)
+        self.profile_every = 0  # > 0: device events around the launches of every profile_every-th step
+        self._kernel_evs: list = []
+        self.tables_built = 0
+        self._selectors: dict = {}
+        self._windows: list = []
+        if self.prep_stream is None:
+            return
+        self._replica_key, self._hbm, self.replica_shared = _acquire_replica(
+            source, self.nbytes, self.device, self.prep_stream, float(hbm_fraction), chunk_bytes)
+        self.load_s = _REPLICAS[self._replica_key][2]
+        try:
+            n = self.n_documents
+            scratch = _native.hip().token_stream_table_scratch(n)
+            table_bytes = 8 * (2 * (n + 1) + scratch)
+            free, _ = torch.cuda.mem_get_info(self.device)
+            if table_bytes > float(hbm_fraction) * free:
+                raise DDLError(f"the two epoch tables ({table_bytes} bytes) exceed hbm_fraction={hbm_fraction} of "
+                               f"the free HBM ({free} bytes free)")
+            self._offs_dev = _replica_offsets(self._replica_key, self._offs_t, self.device, self.prep_stream)
+            with streams.on_stream(self.prep_stream):
+                # two tables: prefetch crosses the epoch boundary (epoch e lives in slot e % 2)
+                self._tables = [torch.empty(n + 1, dtype=torch.int64, device=self.device) for _ in range(2)]
+                self._scratch = torch.empty(scratch, dtype=torch.int64, device=self.device)
+                self._table_epoch = [None, None]
+                self._plan_bytes, self._batch_bytes = token_stream_bytes(self.LB, self.seq_len, self.max_segments,
+                                                                         labels=self.labels)
+                self._windows = [torch.empty(self._plan_bytes, dtype=torch.uint8, device=self.device)
+                                 for _ in range(self.depth + 1)]
+        except Exception:
+            self.close()
+            raise
+
+    # ---------------------------------------------------------------- order
+    def _perm(self, epoch: int) -> FeistelPermutation | None:
+        return FeistelPermutation(self.n_documents, self.seed, epoch) if self.order.shuffle else None
+
+    def _selector(self, epoch: int) -> dict:
+        """The ``RowIndex`` arguments of epoch ``epoch``'s document order (its Feistel round keys), base 0."""
+        sel = self._selectors.get(epoch)
+        if sel is None:
+            if len(self._selectors) > 8:
+                self._selectors.clear()
+            perm = self._perm(epoch)
+            sel = dict(mode=2, idx=0, base=0, **perm.device_args()) if perm is not None else dict(
+                mode=0, idx=0, base=0, keys=[0] * 6, n_domain=1, half_bits=1)
+            self._selectors[epoch] = sel
+        return sel
+
+    def _table(self, epoch: int, sel: dict) -> torch.Tensor:
+        """Epoch ``epoch``'s table, built on the prep stream (the current one) the first time a step of the epoch
+        is assembled. The slot's earlier epoch is two behind: every step that reads it was enqueued before."""
+        k = epoch % 2
+        if self._table_epoch[k] != epoch:
+            _native.hip().token_stream_table(
+                corpus_offsets=self._offs_dev.data_ptr(), n_corpus=self.n_documents, n=self.n_documents,
+                table=self._tables[k].data_ptr(), tile_sums=self._scratch.data_ptr(),
+                stream=self.prep_stream.cuda_stream, **sel)
+            self._table_epoch[k] = epoch
+            self.tables_built += 1
+        return self._tables[k]
+
+    def _assemble(self, t: int):
+        t_host = time.perf_counter()
+        e, g = divmod(t, self.order.batches_per_epoch)
+        row_base = g * self.GB + self.rank * self.LB
+        st = self.prep_stream
+        if st is None:  # the CPU twin: the definition itself
+            r = ref_stream_tokens(self._toks, self._offs_t, perm=self._perm(e), row_base=row_base, rows=self.LB,
+                                  seq_len=self.seq_len, pad_id=self.pad_id, max_segs=self.max_segments,
+                                  labels=self.labels, ignore_index=self.ignore_index)
+            ev = None
+        else:
+            timed = self.profile_every > 0 and t % self.profile_every == 0
+            win = self._windows[t % len(self._windows)]
+            sel = self._selector(e)
+            with streams.on_stream(st):
+                table = self._table(e, sel)
+                # one allocation for everything the caller may hold (outputs, cu_seqlens, counts): a held batch
+                # survives the ring of plan windows
+                whole = torch.empty(self._batch_bytes, dtype=torch.uint8, device=self.device)
+                if timed:
+                    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    ev0.record(st)
+                r = launch_stream_plan(
+                    win.data_ptr(), whole, corpus_ptr=self._hbm.data_ptr(), corpus_elems=self.n_elems,
+                    tok16=self.source.token_bytes == 2, corpus_offsets_ptr=self._offs_dev.data_ptr(),
+                    n_corpus=self.n_documents, table_ptr=table.data_ptr(), selector=sel, row_base=row_base,
+                    rows=self.LB, seq_len=self.seq_len, pad_id=self.pad_id, max_segs=self.max_segments,
+                    stream=st.cuda_stream, labels=self.labels, ignore_index=self.ignore_index)
+                if timed:
+                    ev1.record(st)
+                    self._kernel_evs.append((ev0, ev1))
+                ev = torch.cuda.Event()
+                ev.record(st)
+        counts = r.pop("counts")
+        r["max_seqlen"] = self._max_seqlen  # a static upper bound (varlen attention accepts one)
+        r["n_tokens"], r["n_rows"], r["n_seg"] = counts[2], counts[0], counts[1]
+        self.assemble_s += time.perf_counter() - t_host
+        return r, ev
+
+    # ----------------------------------------------------------- checkpoint
+    def state_dict(self) -> dict:
+        return {
+            "version": STATE_VERSION,
+            "kind": "token_stream",
+            "seed": self.seed,
+            "order_seed": self.seed,
+            "epoch": self.epoch,
+            "global_batch_cursor": self.cursor + (1 if self._pending else 0),
+            "batches_per_epoch": self.order.batches_per_epoch,
+            "global_batch": self.GB,
+            "seq_len": self.seq_len,
+            "n_documents": self.n_documents,
+            "total_tokens": self.total_tokens,
+            "shuffle": self.order.shuffle,
+            "world_size": self.W,
+        }
+
+    def _apply_state(self, sd: dict) -> None:
+        if sd.get("kind") != "token_stream" or sd.get("version") != STATE_VERSION:
+            raise ValueError(f"not a token stream loader state (kind={sd.get('kind')!r}): rows of the token stream "
+                             "and batches of sequences do not share a cursor")
+        for key, mine in (("global_batch", self.GB), ("seq_len", self.seq_len), ("n_documents", self.n_documents),
+                          ("total_tokens", self.total_tokens), ("order_seed", self.seed),
+                          ("shuffle", self.order.shuffle)):
+            if sd.get(key) is not None and sd[key] != mine:
+                raise ValueError(f"checkpoint {key}={sd[key]} does not match {mine}")
+        self.epoch, self.cursor = int(sd["epoch"]), int(sd["global_batch_cursor"])
+        if self.cursor >= self.order.batches_per_epoch:
+            self.epoch, self.cursor = self.epoch + 1, 0
+
+    # ---------------------------------------------------------------- misc
+    @property
+    def replica_ptr(self) -> int | None:
+        """Device address of the corpus replica (None on the CPU, and after ``close``)."""
+        return self._hbm.data_ptr() if self._replica_key is not None else None
+
+    def timing(self) -> dict:
+        """``host_us_per_step``: mean wall time of ``_assemble`` (the launches, on the host); ``kernel_us``: mean
+        device time of the sampled steps' launches (``profile_every``; an epoch's first step includes its table),
+        None without samples. Synchronises the prep stream."""
+        steps = max(1, self.batches + len(self._queue))
+        out = {"host_us_per_step": 1e6 * self.assemble_s / steps, "kernel_us": None,
+               "kernel_samples": len(self._kernel_evs)}
+        if self._kernel_evs:
+            self.prep_stream.synchronize()
+            out["kernel_us"] = 1e3 * sum(a.elapsed_time(b) for a, b in self._kernel_evs) / len(self._kernel_evs)
+        return out
+
+    def stats(self) -> dict:
+        return {"batches": self.batches, "source_bytes": self.nbytes, "load_s": self.load_s,
+                "load_gbps": self.nbytes / self.load_s / 1e9 if self.load_s > 0 else 0.0, "handoff": self.handoff,
+                "host_waits": self.host_waits, "replica_shared": self.replica_shared, "format": "stream",
+                "rows_per_epoch": self.order.n_samples, "max_segments": self.max_segments,
+                "tables_built": self.tables_built}
+
+    def close(self) -> None:
+        if getattr(self, "prep_stream", None) is not None:
+            self.prep_stream.synchronize()
+        if hasattr(self, "_queue"):
+            self._queue.clear()
+        self._kernel_evs = []
+        self._windows = []
+        self._tables = self._scratch = None
+        if getattr(self, "_replica_key", None) is not None:
+            key, self._replica_key = self._replica_key, None
+            self._hbm = None
+            self._offs_dev = None
+            _release_replica(key)
+
+    def __del__(self):  # pragma: no cover - best effort
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -32,6 +32,11 @@ checkpoint. ``DDL_DEVICE=cpu`` runs it (and ``--zero-copy``) with the host twin.
 only issues launches. Packing is in-order, shapes are static (fixed rows, ``cu_seqlens`` of fixed capacity) and
 ``n_tokens`` / ``n_rows`` / ``n_seg`` are 0-d device tensors; ``max_seqlen`` is an upper bound.
 
+``--resident --stream`` delivers the GPT pre-training format instead (``ResidentTokenStreamLoader``): the epoch's
+shuffled documents concatenated and cut every ``seq_len`` tokens, so ``--global-batch`` counts ROWS, every row is
+full (100% dense, static shapes) and a segment is a run of one document inside one row. The stream's table and
+each batch's plan are built on the GPU; the checkpoint is ``kind="token_stream"``.
+
 ``--labels`` (with ``--resident`` or ``--zero-copy``) asks the loader for the next-token targets as well
 (``labels=True``: int64 ``labels``, ``-100`` where a position has no target -- the end of a row or of a segment,
 padding) and trains a toy embedding + linear model on every batch with ``cross_entropy(ignore_index=-100)``.
@@ -64,6 +69,9 @@ def main() -> None:
     ap.add_argument("--device-plan", action="store_true",
                     help="with --resident: the batch's order and pack plan are built on the GPU too (in-order "
                          "packing, static shapes, counts as device scalars)")
+    ap.add_argument("--stream", action="store_true",
+                    help="with --resident: full rows cut from the concatenated shuffled documents "
+                         "(--global-batch counts rows)")
     ap.add_argument("--labels", action="store_true",
                     help="with --resident or --zero-copy: the loader also delivers next-token labels, and every "
                          "batch runs a tiny embedding -> linear -> cross_entropy step on them")
@@ -75,6 +83,8 @@ def main() -> None:
         ap.error("--zero-copy and --resident are two loaders: pick one")
     if a.device_plan and not a.resident:
         ap.error("--device-plan is a mode of --resident")
+    if a.stream and (not a.resident or a.device_plan or a.mode != "pack"):
+        ap.error("--stream is a format of --resident (packed rows by construction; it has no --device-plan mode)")
     if a.labels and not (a.zero_copy or a.resident):
         ap.error("--labels needs --resident or --zero-copy (the producer path does not deliver labels)")
     vocab = a.vocab or (512 if a.labels else 50257)
@@ -94,7 +104,9 @@ def main() -> None:
                 n_tok = int(offs.tensor()[-1])
                 src = SharedTokenSource(SharedArraySource(name + "_tok", n_tok, (1,), "int32"), offs, a.seq_len)
             pack_order = "ffd" if a.mode == "pack" else "in_order"
-            if a.resident and a.device_plan:  # first-fit-decreasing is a host plan
+            if a.stream:
+                dl = ddl_amd.ResidentTokenStreamLoader(src, a.global_batch, a.seq_len, env, n_epochs=a.epochs, **lab_kw)
+            elif a.resident and a.device_plan:  # first-fit-decreasing is a host plan
                 dl = ddl_amd.ResidentTokenLoader(src, a.global_batch, a.seq_len, a.mode, env, n_epochs=a.epochs,
                                                  plan="device", **lab_kw)
             elif a.resident:
