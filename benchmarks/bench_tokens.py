@@ -59,6 +59,9 @@ def main(argv=None):
     ap.add_argument("--stream", action="store_true",
                     help="resident: the token stream format (ResidentTokenStreamLoader): --batch counts ROWS per rank "
                          "per step, cut from the concatenated shuffled documents; table, plan and pack are launches")
+    ap.add_argument("--shuffle-rows", action="store_true",
+                    help="with --stream: the epoch's rows in a shuffled order (shuffle_rows=True: the per-row plan "
+                         "kernels in place of the contiguous plan)")
     ap.add_argument("--max-blocks", type=int, default=None,
                     help="zerocopy: grid cap of the gather kernel (0 = uncapped; default: the loader's)")
     ap.add_argument("--labels", action="store_true",
@@ -73,6 +76,8 @@ def main(argv=None):
         ap.error("--plan device needs --path resident")
     if a.stream and (not resident or a.plan != "host" or a.mode != "pack"):
         ap.error("--stream needs --path resident, and is neither --plan device nor --mode pad")
+    if a.shuffle_rows and not a.stream:
+        ap.error("--shuffle-rows needs --stream")
     if a.plan == "device" and a.mode == "pack":
         if a.pack_order != "in_order":
             ap.error("--plan device builds the in-order plan: pass --pack-order in_order")
@@ -120,7 +125,8 @@ def main(argv=None):
             n_epochs = (a.warmup + a.steps + a.idle_steps + a.warmup // 2) // (a.n_seqs // gb) + 2
             pack_order = a.pack_order if a.mode == "pack" else "in_order"
             if a.stream:
-                dl = ddl_amd.ResidentTokenStreamLoader(source, gb, a.seq_len, env, labels=a.labels)
+                dl = ddl_amd.ResidentTokenStreamLoader(source, gb, a.seq_len, env, labels=a.labels,
+                                                       shuffle_rows=a.shuffle_rows)
                 dl.profile_every = a.kernel_sample
             elif resident:
                 dl = ddl_amd.ResidentTokenLoader(source, gb, a.seq_len, a.mode, env, pack_order=pack_order,
@@ -240,7 +246,7 @@ def main(argv=None):
                                 "replica_shared": st["replica_shared"], "plan": "stream" if a.stream else a.plan}
                     if a.stream:
                         per_path.update(format="stream", max_segments=st["max_segments"],
-                                        tables_built=st["tables_built"])
+                                        tables_built=st["tables_built"], shuffle_rows=st["shuffle_rows"])
                 elif zc:
                     per_path = {"path": "zerocopy", "max_blocks": st["max_blocks"], "host_waits": st["host_waits"],
                                 "prefault_s": round(st["prefault_s"], 3)}

@@ -544,10 +544,13 @@ def token_stream(dev, repeats=5) -> None:
     scan -- ``index_select`` of the lengths by a precomputed device index, then ``cumsum`` -- which needs that
     n-sized index built and uploaded per epoch (not timed here). (2) ``token_stream_plan`` at 64 and 2048 rows of
     4096 tokens over the ``tokens_plan`` corpus (131072 documents), against ``token_batch_descriptor`` +
-    ``pack_plan_device`` at 64 and 2048 sequences, and the whole two-launch stream route (plan + pack). 4 windows
-    issued round-robin at launcher level: device times."""
+    ``pack_plan_device`` at 64 and 2048 sequences, and the whole two-launch stream route (plan + pack). (3) The
+    shuffled-row plan ``token_stream_plan_rows`` (two launches) and its three-launch route at the same sizes, in
+    the same rounds as the contiguous plan and route, and the emit kernel alone over either plan. 4 windows issued
+    round-robin at launcher level: device times."""
     from ddl_amd import _native
-    from ddl_amd.ops.kernels import (_align16, _index_kw, device_plan_bytes, launch_stream_plan,
+    from ddl_amd.ops.kernels import (_align16, _index_kw, _launch_stream_emit, _stream_plan_layout,
+                                     device_plan_bytes, launch_stream_plan, launch_stream_plan_rows,
                                      stream_max_segments, token_stream_bytes)
 
     hip = _native.hip()
@@ -647,6 +650,59 @@ def token_stream(dev, repeats=5) -> None:
             **{k + "_us_min_max": [round(min(t[k] for t in runs) * 1e6, 2), round(max(t[k] for t in runs) * 1e6, 2)]
                for k in med},
             "stream_route_tokens_per_s": round(B * S / med["stream_route"], 1)}), flush=True)
+
+        # shuffled rows (token_stream_plan_rows: two launches, one wave per row) next to the contiguous plan, and
+        # the emit kernel alone over a plan of scattered rows and over one of contiguous rows
+        n_rows = int(offs[-1]) // S
+        row_perm = FeistelPermutation(n_rows, 5, 1)
+        Mr = stream_max_segments(lens, B, S, shuffled_rows=True)
+        rplan_b, rbatch_b = token_stream_bytes(B, S, Mr, shuffled_rows=True)
+        rplans = [torch.empty(rplan_b, dtype=torch.uint8, device=dev) for _ in range(rot)]
+        rwholes = [torch.empty(rbatch_b, dtype=torch.uint8, device=dev) for _ in range(rot)]
+        common = dict(corpus_ptr=corpus.data_ptr(), corpus_elems=corpus.numel(), tok16=True, rows=B, seq_len=S,
+                      pad_id=0, stream=stream)
+        plan_args = dict(corpus_offsets_ptr=coffs.data_ptr(), n_corpus=n_src, table_ptr=table.data_ptr(), selector=sel)
+
+        def rows_route(k):
+            return launch_stream_plan_rows(rplans[k].data_ptr(), rwholes[k], row_selector=_index_kw(None, row_perm,
+                                                                                                    (3 + k) * B),
+                                           stream_rows=n_rows, max_segs=Mr, **plan_args, **common)
+
+        def rows_plan_only(k):
+            o_ss, o_so, o_rs, o_re, o_scr = _stream_plan_layout(rplans[k].data_ptr(), B, Mr)
+            rsel = {"rows_" + key: v for key, v in _index_kw(None, row_perm, (3 + k) * B).items()}
+            hip.token_stream_plan_rows(table=table.data_ptr(), corpus_offsets=coffs.data_ptr(), n_corpus=n_src,
+                                       n=n_src, stream_rows=n_rows, rows=B, seq_len=S, max_segs=Mr, seg_offsets=o_so,
+                                       seg_src=o_ss, row_start=o_rs, row_end=o_re, scratch=o_scr,
+                                       counts=rwholes[k][rbatch_b - 32:].data_ptr(), stream=stream, **sel, **rsel)
+
+        def emit_only(k, shuffled):  # over the plan the route left in the window
+            plan_ptr, whole, cap = ((rplans[k].data_ptr(), rwholes[k], Mr) if shuffled
+                                    else (plans[k].data_ptr(), wholes[k], M))
+            _launch_stream_emit(hip, whole, _stream_plan_layout(plan_ptr, B, cap), max_segs=cap,
+                                position_dtype=torch.int64, labels=False, ignore_index=-100,
+                                plan_fn=lambda **kw: None, plan_kw={}, **common)
+
+        for k in range(rot):
+            route(k)
+            rr = rows_route(k)
+        torch.cuda.synchronize()
+        assert rr["counts"].tolist()[::2] == [B, B * S] and bool(rr["attention_mask"].all()), "row batch not dense"
+        runs = [{"rows_plan": rotating([lambda k=k: rows_plan_only(k) for k in range(rot)]),
+                 "stream_plan": rotating([lambda k=k: plan_only(k) for k in range(rot)]),
+                 "rows_route": rotating([lambda k=k: rows_route(k) for k in range(rot)]),
+                 "stream_route": rotating([lambda k=k: route(k) for k in range(rot)]),
+                 "emit_scattered_rows": rotating([lambda k=k: emit_only(k, True) for k in range(rot)]),
+                 "emit_contiguous_rows": rotating([lambda k=k: emit_only(k, False) for k in range(rot)])}
+                for _ in range(repeats)]
+        med = {k: float(np.median([t[k] for t in runs])) for k in runs[0]}
+        print(json.dumps({
+            "kernel": "token_stream_plan_rows", "rows": B, "seq_len": S, "documents": n_src, "max_segs": Mr,
+            "segments": int(rr["counts"][1]), "repeats": repeats,
+            **{k + "_us_median": round(v * 1e6, 2) for k, v in med.items()},
+            **{k + "_us_min_max": [round(min(t[k] for t in runs) * 1e6, 2), round(max(t[k] for t in runs) * 1e6, 2)]
+               for k in med},
+            "rows_route_tokens_per_s": round(B * S / med["rows_route"], 1)}), flush=True)
 
 
 if __name__ == "__main__":

@@ -844,6 +844,39 @@ PYBIND11_MODULE(_ddl_hip, m) {
       py::arg("base"), py::arg("keys"), py::arg("n_domain"), py::arg("half_bits"), py::arg("n"), py::arg("row_base"),
       py::arg("rows"), py::arg("seq_len"), py::arg("max_segs"), py::arg("seg_offsets"), py::arg("seg_src"),
       py::arg("row_start"), py::arg("row_end"), py::arg("counts"), py::arg("stream"));
+  m.def(
+      "token_stream_plan_rows",
+      [](uintptr_t table, uintptr_t corpus_offsets, int64_t n_corpus, int mode, uintptr_t idx, int64_t base,
+         std::vector<uint64_t> keys, uint64_t n_domain, uint32_t half_bits, int64_t n, int rows_mode,
+         uintptr_t rows_idx, int64_t rows_base, std::vector<uint64_t> rows_keys, uint64_t rows_n_domain,
+         uint32_t rows_half_bits, int64_t stream_rows, int64_t rows, int64_t seq_len, int64_t max_segs,
+         uintptr_t seg_offsets, uintptr_t seg_src, uintptr_t row_start, uintptr_t row_end, uintptr_t counts,
+         uintptr_t scratch, uintptr_t stream) {
+        ddl::StreamRowsSpec sp{};
+        sp.table = as_ptr<const int64_t>(table);
+        sp.corpus_offsets = as_ptr<const int64_t>(corpus_offsets);
+        sp.n_corpus = n_corpus;
+        sp.ri = make_index(mode, idx, base, keys, n_domain, half_bits);
+        sp.n = n;
+        sp.rows_ri = make_index(rows_mode, rows_idx, rows_base, rows_keys, rows_n_domain, rows_half_bits);
+        sp.stream_rows = stream_rows;
+        sp.rows = rows;
+        sp.seq_len = seq_len;
+        sp.max_segs = max_segs;
+        sp.seg_offsets = as_ptr<int64_t>(seg_offsets);
+        sp.seg_src = as_ptr<int64_t>(seg_src);
+        sp.row_start = as_ptr<int64_t>(row_start);
+        sp.row_end = as_ptr<int64_t>(row_end);
+        sp.counts = as_ptr<int64_t>(counts);
+        sp.scratch = as_ptr<int64_t>(scratch);
+        check_rc(ddl::token_stream_plan_rows(sp, as_stream(stream)), "token_stream_plan_rows");
+      },
+      py::arg("table"), py::arg("corpus_offsets"), py::arg("n_corpus"), py::arg("mode"), py::arg("idx"),
+      py::arg("base"), py::arg("keys"), py::arg("n_domain"), py::arg("half_bits"), py::arg("n"),
+      py::arg("rows_mode"), py::arg("rows_idx"), py::arg("rows_base"), py::arg("rows_keys"),
+      py::arg("rows_n_domain"), py::arg("rows_half_bits"), py::arg("stream_rows"), py::arg("rows"),
+      py::arg("seq_len"), py::arg("max_segs"), py::arg("seg_offsets"), py::arg("seg_src"), py::arg("row_start"),
+      py::arg("row_end"), py::arg("counts"), py::arg("scratch"), py::arg("stream"));
   m.attr("TOKEN_SEG_LDS_CAP") = ddl::kTiSegCap;
   m.attr("RAGGED_MAP_CAP") = ddl::kRaggedMapCap;
   m.def(

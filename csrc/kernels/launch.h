@@ -218,6 +218,39 @@ struct StreamPlanSpec {
 };
 int token_stream_plan(const StreamPlanSpec& spec, hipStream_t st);
 
+// tokens_stream_rows.hip ----------------------------------------------------
+// token_stream_plan for rows picked anywhere in the stream: batch row k is stream row rho_k = source_row(rows_ri,
+// k) (mode 0: base + k; mode 1: a device index of `rows` entries, repeats allowed; mode 2: a Feistel permutation of
+// [0, stream_rows) at position base + k), i.e. the window [rho_k * seq_len, (rho_k + 1) * seq_len). Two launches on
+// `st` of ceil(rows / 16) workgroups, one wave per row (the rows' documents counted, then the plan written behind
+// a per-workgroup reduction of the counts): no atomics, no waiting between workgroups. Writes the plan arrays of
+// token_stream_plan in the same layout, so pad_pack_tokens_indexed is called as for it: segments numbered
+// row-major over the batch's rows, row_start / row_end [k] = k * seq_len, (k + 1) * seq_len, counts = {rows, n_seg,
+// rows * seq_len, longest segment}. Only full rows can be selected: rho_k < 0 or (rho_k + 1) * seq_len > table[n]
+// makes the batch invalid -- counts[0] = -1 and counts[1 .. 3] taken over the valid rows, seg_offsets[0] = 0 and
+// no other segment entry written -- as does n_seg > max_segs (nothing written past the capacity).
+// stream_rows: the full rows of the stream as the host knows them, the domain a mode 2 rows_ri must have.
+// scratch: 4 * rows int64 of device memory between the two launches.
+struct StreamRowsSpec {
+  const int64_t* table;           // [n + 1], token_stream_table of the same ri and n
+  const int64_t* corpus_offsets;  // [n_corpus + 1], device
+  int64_t n_corpus;
+  RowIndex ri;       // the documents' order
+  int64_t n;
+  RowIndex rows_ri;  // the rows' selection
+  int64_t stream_rows;
+  int64_t rows;
+  int64_t seq_len;
+  int64_t max_segs;      // seg_offsets holds max_segs + 1 entries, seg_src max_segs
+  int64_t* seg_offsets;  // out
+  int64_t* seg_src;      // out
+  int64_t* row_start;    // out: [rows]
+  int64_t* row_end;      // out: [rows]
+  int64_t* counts;       // out: [4]
+  int64_t* scratch;      // [4 * rows]
+};
+int token_stream_plan_rows(const StreamRowsSpec& spec, hipStream_t st);
+
 // ragged.hip ----------------------------------------------------------------
 // Device twin of the host gather_ragged: sequence i (src_start[i] elements into src, dst_offsets[i + 1] -
 // dst_offsets[i] elements of elem_bytes = 2 or 4) -> dst[dst_offsets[i] ...). src: HBM or pinned,

@@ -1295,25 +1295,59 @@ def _stream_lengths(offs: np.ndarray, q: np.ndarray) -> np.ndarray:
     return np.maximum(offs[q + 1] - offs[q], 0) if q.size else np.zeros(0, dtype=np.int64)
 
 
-def _stream_default_segs(n: int, rows: int, seq_len: int) -> int:
-    """A capacity that needs no length: every document that touches a window holds one of its tokens."""
-    return max(1, min(int(n), int(rows) * int(seq_len)) + int(rows) - 1)
+def _stream_default_segs(n: int, rows: int, seq_len: int, shuffled_rows: bool = False) -> int:
+    """A capacity that needs no length: every document that touches a window holds one of its tokens. Shuffled
+    rows: every row may cut a document at either end, and a segment holds at least one token."""
+    n, rows, seq_len = int(n), int(rows), int(seq_len)
+    if shuffled_rows:
+        return max(1, min(min(n, rows * seq_len) + 2 * rows, rows * seq_len))
+    return max(1, min(n, rows * seq_len) + rows - 1)
 
 
-def stream_max_segments(lengths, rows: int, seq_len: int) -> int:
+def stream_max_segments(lengths, rows: int, seq_len: int, shuffled_rows: bool = False) -> int:
     """The most segments a ``rows x seq_len`` window of the token stream can hold, in any document order: with
     ``k`` = the largest count of smallest non-empty lengths whose sum is ``<= rows * seq_len``, at most ``k`` + 2
     documents touch a window (``k`` inside it, one cut at either end), and each of the ``rows`` - 1 interior row
-    boundaries splits at most one of them: ``min(k + 2, n_nonempty) + rows - 1`` (at least 1)."""
+    boundaries splits at most one of them: ``min(k + 2, n_nonempty) + rows - 1`` (at least 1).
+
+    ``shuffled_rows``: the bound for ``rows`` distinct rows picked anywhere in the stream (``row_perm`` /
+    ``row_index`` of ``ref_stream_tokens``): the documents lying wholly inside the selected rows are distinct and
+    total at most ``rows * seq_len`` tokens, at most ``min(k, n_nonempty)`` of them, and every row has at most one
+    document cut at either end: ``max(1, min(k, n_nonempty) + 2 * rows)``. It covers distinct rows only: with a
+    row repeated in ``row_index`` its whole documents count once per occurrence, the caller sizes ``max_segs`` and
+    an overflow is reported as ``n_rows`` = -1."""
     lens = np.asarray(lengths, dtype=np.int64).reshape(-1)
     lens = np.sort(lens[lens > 0])
     k = int(np.searchsorted(np.cumsum(lens), int(rows) * int(seq_len), side="right"))
+    if shuffled_rows:
+        return max(1, min(k, int(lens.size)) + 2 * int(rows))
     return max(1, min(k + 2, int(lens.size)) + int(rows) - 1)
+
+
+def _stream_row_select(row_perm, row_index, row_base: int, rows: int) -> np.ndarray | None:
+    """The stream rows ``rho_k`` of a batch selected by ``row_perm`` / ``row_index`` (None: contiguous rows)."""
+    if row_perm is None and row_index is None:
+        return None
+    if row_perm is not None and row_index is not None:
+        raise ValueError("give either row_perm or row_index, not both")
+    if row_index is not None:
+        if int(row_base) != 0:
+            raise ValueError("row_index selects the batch's rows itself: row_base must be 0")
+        rho = (row_index.detach().cpu().numpy() if isinstance(row_index, torch.Tensor) else np.asarray(row_index))
+        if rho.dtype != np.int64:
+            raise TypeError("row_index must be int64")
+        rho = rho.reshape(-1)
+        if rho.size != int(rows):
+            raise ValueError(f"row_index holds {rho.size} entries for {int(rows)} rows")
+        return rho
+    if int(row_base) + int(rows) > row_perm.n:
+        raise IndexError("row_perm positions out of range")
+    return np.asarray(row_perm(np.arange(int(row_base), int(row_base) + int(rows), dtype=np.int64)), dtype=np.int64)
 
 
 def ref_stream_tokens(corpus: torch.Tensor, corpus_offsets, *, perm=None, row_base: int, rows: int, seq_len: int,
                       pad_id: int = 0, position_dtype=torch.int64, max_segs: int | None = None, labels: bool = False,
-                      ignore_index: int = -100) -> dict:
+                      ignore_index: int = -100, row_perm: FeistelPermutation | None = None, row_index=None) -> dict:
     """The definition of the token stream format, in NumPy on the CPU (no plan code is involved)::
 
         stream = concat(corpus[offs[q_i] : offs[q_i + 1]] for i in range(n)),  q_i = perm(i) (or i),  T = len(stream)
@@ -1328,19 +1362,42 @@ def ref_stream_tokens(corpus: torch.Tensor, corpus_offsets, *, perm=None, row_ba
     token count) and ``counts`` = int64 ``[n_rows, n_seg, n_tokens, max_seg]`` (``n_rows``: the rows holding a
     token); ``labels=True`` adds ``labels`` = ``ref_token_labels`` of the batch. ``n_seg > max_segs`` is an
     overflow: ``n_rows`` = -1, every row padding, ``cu_seqlens`` all zero, labels all ``ignore_index``.
-    ``max_segs`` None: ``min(n, rows * S) + rows - 1``, which no window exceeds."""
+    ``max_segs`` None: ``min(n, rows * S) + rows - 1``, which no window exceeds.
+
+    Shuffled rows: with ``row_perm`` (a ``FeistelPermutation`` of the stream's ``T // S`` full rows) or ``row_index``
+    (int64, ``rows`` entries, ``row_base`` 0; giving both is a ``ValueError``) batch row ``k`` is stream row
+    ``rho_k = row_perm(row_base + k)`` or ``row_index[k]``::
+
+        row k  = stream[rho_k * S : (rho_k + 1) * S]
+
+    Segments keep their rule and are numbered row-major over the batch's rows in batch order; a row repeated in
+    ``row_index`` makes its own segments at every occurrence. Only full rows can be selected: ``rho_k < 0`` or
+    ``(rho_k + 1) * S > T`` (the partial last row and everything past it) makes the batch invalid, reported like
+    an overflow (``n_rows`` = -1, every row padding, ``cu_seqlens`` all zero, labels all ``ignore_index``) with
+    ``n_seg``, ``n_tokens`` and ``max_seg`` taken over the valid rows only; a valid batch has ``counts`` =
+    ``[rows, n_seg, rows * S, max_seg]``. ``max_segs`` None: ``min(min(n, rows * S) + 2 * rows, rows * S)``."""
     S, R, base = int(seq_len), int(rows), int(row_base)
     if S <= 0 or R < 1 or base < 0:
         raise ValueError("seq_len must be > 0, rows >= 1 and row_base >= 0")
+    rho = _stream_row_select(row_perm, row_index, base, R)
     offs = torch.as_tensor(corpus_offsets).to("cpu", torch.int64).reshape(-1).numpy()
     n = offs.size - 1
     q = _stream_order(n, perm)
     lens = _stream_lengths(offs, q)
     table = np.concatenate([np.zeros(1, dtype=np.int64), np.cumsum(lens, dtype=np.int64)])
-    M = _stream_default_segs(n, R, S) if max_segs is None else int(max_segs)
-    g = base * S + np.arange(R * S, dtype=np.int64)
-    n_tok = int(np.count_nonzero(g < table[-1]))  # the valid positions are a prefix of the batch
-    gv = g[:n_tok]
+    M = _stream_default_segs(n, R, S, rho is not None) if max_segs is None else int(max_segs)
+    if rho is None:
+        g = base * S + np.arange(R * S, dtype=np.int64)
+        live = g < table[-1]  # the valid positions are a prefix of the batch
+        rows_ok = True
+    else:
+        row_ok = (rho >= 0) & (rho < table[-1] // S)  # full rows only
+        g = (np.where(row_ok, rho, 0)[:, None] * S + np.arange(S, dtype=np.int64)).reshape(-1)
+        live = np.repeat(row_ok, S)
+        rows_ok = bool(row_ok.all())
+    at = np.flatnonzero(live)  # batch positions of the tokens; the counts of an invalid batch are the valid rows'
+    n_tok = int(at.size)
+    gv = g[at]
     d = np.searchsorted(table, gv, side="right") - 1  # the last document starting at or before g: never an empty one
     new = np.ones(n_tok, dtype=bool)
     new[1:] = (d[1:] != d[:-1]) | (gv[1:] % S == 0)
@@ -1348,7 +1405,7 @@ def ref_stream_tokens(corpus: torch.Tensor, corpus_offsets, *, perm=None, row_ba
     n_seg = int(starts.size)
     seg = np.cumsum(new) - 1
     local = np.arange(n_tok, dtype=np.int64)
-    ok = n_seg <= M
+    ok = n_seg <= M and rows_ok
     ids = np.full(R * S, int(pad_id), dtype=np.int32)
     mask = np.zeros(R * S, dtype=np.uint8)
     pos = np.zeros(R * S, dtype=np.int64)
@@ -1356,12 +1413,12 @@ def ref_stream_tokens(corpus: torch.Tensor, corpus_offsets, *, perm=None, row_ba
     cu = np.zeros(M + 1, dtype=np.int32)
     if ok and n_tok:
         flat = widen_tokens(corpus.cpu().reshape(-1)).numpy()
-        ids[:n_tok] = flat[offs[q[d]] + (gv - table[d])]
-        mask[:n_tok] = 1
-        pos[:n_tok] = local - starts[seg]
-        sid[:n_tok] = seg
+        ids[at] = flat[offs[q[d]] + (gv - table[d])]
+        mask[at] = 1
+        pos[at] = local - starts[seg]
+        sid[at] = seg
     if ok:
-        cu[:n_seg] = starts
+        cu[:n_seg] = at[starts]
         cu[n_seg:] = n_tok
     max_seg = int(np.diff(np.append(starts, n_tok)).max()) if n_seg else 0
     counts = torch.tensor([-(-n_tok // S) if ok else -1, n_seg, n_tok, max_seg], dtype=torch.int64)
@@ -1416,38 +1473,39 @@ def token_stream_table(corpus_offsets: torch.Tensor, perm: FeistelPermutation | 
 
 
 def token_stream_bytes(rows: int, seq_len: int, max_segs: int, position_dtype=torch.int64,
-                       labels: bool = False) -> tuple[int, int]:
+                       labels: bool = False, shuffled_rows: bool = False) -> tuple[int, int]:
     """(plan bytes, batch bytes) of one token stream batch. The plan -- seg_src [max_segs], seg_offsets
     [max_segs + 1], row_start / row_end [rows] -- lives between the two launches and nothing a caller holds is
     there; the batch is ``device_batch_bytes``: the outputs, ``cu_seqlens`` of capacity ``max_segs`` + 1 and the
-    four int64 counts."""
+    four int64 counts. ``shuffled_rows``: the plan of ``token_stream_plan_rows``, which keeps four more int64 per
+    row between its two launches."""
     plan = _align16(8 * max_segs) + _align16(8 * (max_segs + 1)) + 2 * _align16(8 * rows)
+    if shuffled_rows:
+        plan += _align16(8 * 4 * rows)
     return plan, device_batch_bytes(rows, seq_len, max_segs, position_dtype, labels)
 
 
-def launch_stream_plan(plan_ptr: int, whole: torch.Tensor, *, corpus_ptr: int, corpus_elems: int, tok16: bool,
-                       corpus_offsets_ptr: int, n_corpus: int, table_ptr: int, selector: dict, row_base: int,
-                       rows: int, seq_len: int, pad_id: int, max_segs: int, position_dtype=torch.int64,
-                       stream: int = 0, labels: bool = False, ignore_index: int = -100) -> dict:
-    """The two launches of one token stream batch on raw stream ``stream``: ``token_stream_plan`` and
-    ``pad_pack_tokens_indexed`` (pack mode, counts read from device memory). ``plan_ptr`` / ``whole``: the two
-    sizes of ``token_stream_bytes``, 16-byte aligned device memory; ``selector``: the ``RowIndex`` of the epoch's
-    order with base 0, the one ``table_ptr``'s table was built with. Nothing here allocates, copies or
-    synchronises. Returns the dict of ``stream_tokens_indexed_device``."""
-    h = _native.hip()
-    S, R, M = int(seq_len), int(rows), int(max_segs)
-    ignore_index = _label_args(labels, ignore_index)
+def _stream_plan_layout(plan_ptr: int, rows: int, max_segs: int) -> tuple[int, int, int, int, int]:
+    """Addresses of seg_src, seg_offsets, row_start, row_end and (shuffled rows) the per-row scratch in a plan."""
     o_ss = plan_ptr
-    o_so = o_ss + _align16(8 * M)
-    o_rs = o_so + _align16(8 * (M + 1))
-    o_re = o_rs + _align16(8 * R)
+    o_so = o_ss + _align16(8 * max_segs)
+    o_rs = o_so + _align16(8 * (max_segs + 1))
+    o_re = o_rs + _align16(8 * rows)
+    return o_ss, o_so, o_rs, o_re, o_re + _align16(8 * rows)
+
+
+def _launch_stream_emit(h, whole: torch.Tensor, plan: tuple, *, corpus_ptr: int, corpus_elems: int, tok16: bool,
+                        rows: int, seq_len: int, pad_id: int, max_segs: int, position_dtype, stream: int,
+                        labels: bool, ignore_index: int, plan_fn, plan_kw: dict) -> dict:
+    """``plan_fn(counts=..., **plan_kw)`` and ``pad_pack_tokens_indexed`` over the plan it wrote (pack mode, counts
+    read from device memory), with everything returned carved from ``whole``."""
+    S, R, M = int(seq_len), int(rows), int(max_segs)
+    o_ss, o_so, o_rs, o_re, _ = plan
     out_b = token_output_bytes(R, S, M, position_dtype, labels)
     ids, mask, pos, seg, cu, *lab = carve_token_outputs(whole, R, S, M, position_dtype, labels)
     counts = whole[out_b:out_b + 32].view(torch.int64)
     c_ptr = counts.data_ptr()
-    h.token_stream_plan(table=table_ptr, corpus_offsets=corpus_offsets_ptr, n_corpus=n_corpus, n=n_corpus,
-                        row_base=int(row_base), rows=R, seq_len=S, max_segs=M, seg_offsets=o_so, seg_src=o_ss,
-                        row_start=o_rs, row_end=o_re, counts=c_ptr, stream=stream, **selector)
+    plan_fn(counts=c_ptr, **plan_kw)
     h.pad_pack_tokens_indexed(
         corpus=corpus_ptr, corpus_elems=corpus_elems, src_start=0, seg_src=o_ss, offsets=0, row_start=o_rs,
         row_end=o_re, seg_offsets=o_so, n_seg=0, out_tokens=ids.data_ptr(), attn_mask=mask.data_ptr(),
@@ -1462,11 +1520,59 @@ def launch_stream_plan(plan_ptr: int, whole: torch.Tensor, *, corpus_ptr: int, c
     return r
 
 
+def launch_stream_plan(plan_ptr: int, whole: torch.Tensor, *, corpus_ptr: int, corpus_elems: int, tok16: bool,
+                       corpus_offsets_ptr: int, n_corpus: int, table_ptr: int, selector: dict, row_base: int,
+                       rows: int, seq_len: int, pad_id: int, max_segs: int, position_dtype=torch.int64,
+                       stream: int = 0, labels: bool = False, ignore_index: int = -100) -> dict:
+    """The two launches of one token stream batch on raw stream ``stream``: ``token_stream_plan`` and
+    ``pad_pack_tokens_indexed`` (pack mode, counts read from device memory). ``plan_ptr`` / ``whole``: the two
+    sizes of ``token_stream_bytes``, 16-byte aligned device memory; ``selector``: the ``RowIndex`` of the epoch's
+    order with base 0, the one ``table_ptr``'s table was built with. Nothing here allocates, copies or
+    synchronises. Returns the dict of ``stream_tokens_indexed_device``."""
+    h = _native.hip()
+    S, R, M = int(seq_len), int(rows), int(max_segs)
+    ignore_index = _label_args(labels, ignore_index)
+    plan = _stream_plan_layout(plan_ptr, R, M)
+    o_ss, o_so, o_rs, o_re, _ = plan
+    plan_kw = dict(table=table_ptr, corpus_offsets=corpus_offsets_ptr, n_corpus=n_corpus, n=n_corpus,
+                   row_base=int(row_base), rows=R, seq_len=S, max_segs=M, seg_offsets=o_so, seg_src=o_ss,
+                   row_start=o_rs, row_end=o_re, stream=stream, **selector)
+    return _launch_stream_emit(h, whole, plan, corpus_ptr=corpus_ptr, corpus_elems=corpus_elems, tok16=tok16, rows=R,
+                               seq_len=S, pad_id=pad_id, max_segs=M, position_dtype=position_dtype, stream=stream,
+                               labels=labels, ignore_index=ignore_index, plan_fn=h.token_stream_plan, plan_kw=plan_kw)
+
+
+def launch_stream_plan_rows(plan_ptr: int, whole: torch.Tensor, *, corpus_ptr: int, corpus_elems: int, tok16: bool,
+                            corpus_offsets_ptr: int, n_corpus: int, table_ptr: int, selector: dict,
+                            row_selector: dict, stream_rows: int, rows: int, seq_len: int, pad_id: int,
+                            max_segs: int, position_dtype=torch.int64, stream: int = 0, labels: bool = False,
+                            ignore_index: int = -100) -> dict:
+    """``launch_stream_plan`` for rows picked anywhere in the stream: the two launches of ``token_stream_plan_rows``
+    and ``pad_pack_tokens_indexed``, the call it is for contiguous rows. ``plan_ptr``: the plan size of
+    ``token_stream_bytes(..., shuffled_rows=True)``; ``row_selector``: the ``RowIndex`` arguments that select the
+    batch's rows (``_index_kw`` of a device ``row_index``, or of ``row_perm`` at the batch's first position);
+    ``stream_rows``: the stream's full rows, ``T // seq_len``. Nothing here allocates, copies or synchronises."""
+    h = _native.hip()
+    S, R, M = int(seq_len), int(rows), int(max_segs)
+    ignore_index = _label_args(labels, ignore_index)
+    plan = _stream_plan_layout(plan_ptr, R, M)
+    o_ss, o_so, o_rs, o_re, o_scr = plan
+    plan_kw = dict(table=table_ptr, corpus_offsets=corpus_offsets_ptr, n_corpus=n_corpus, n=n_corpus,
+                   stream_rows=int(stream_rows), rows=R, seq_len=S, max_segs=M, seg_offsets=o_so, seg_src=o_ss,
+                   row_start=o_rs, row_end=o_re, scratch=o_scr, stream=stream, **selector,
+                   **{"rows_" + k: v for k, v in row_selector.items()})
+    return _launch_stream_emit(h, whole, plan, corpus_ptr=corpus_ptr, corpus_elems=corpus_elems, tok16=tok16, rows=R,
+                               seq_len=S, pad_id=pad_id, max_segs=M, position_dtype=position_dtype, stream=stream,
+                               labels=labels, ignore_index=ignore_index, plan_fn=h.token_stream_plan_rows,
+                               plan_kw=plan_kw)
+
+
 def stream_tokens_indexed_device(corpus: torch.Tensor, corpus_offsets: torch.Tensor, table: torch.Tensor | None = None,
                                  *, perm: FeistelPermutation | None = None, row_base: int, rows: int, seq_len: int,
                                  pad_id: int = 0, max_segs: int | None = None, position_dtype=torch.int64,
                                  labels: bool = False, ignore_index: int = -100, out: torch.Tensor | None = None,
-                                 stream=None) -> dict:
+                                 stream=None, row_perm: FeistelPermutation | None = None,
+                                 row_index: torch.Tensor | None = None, stream_rows: int | None = None) -> dict:
     """Rows ``[row_base, row_base + rows)`` of the token stream (``ref_stream_tokens``, the definition) out of a
     corpus in HBM: ``corpus`` (flat int32 / 16-bit ids), ``corpus_offsets`` (int64 [n + 1]) and ``table``
     (``token_stream_table`` of the same ``perm``) are device tensors. Two launches -- ``token_stream_plan`` and
@@ -1475,7 +1581,15 @@ def stream_tokens_indexed_device(corpus: torch.Tensor, corpus_offsets: torch.Ten
     everything returned are carved from, else one allocation. The result is static-shaped ([rows, seq_len],
     ``cu_seqlens`` of ``max_segs`` + 1 entries) and holds no padding except past the stream's end. ``max_segs``
     None: ``min(n, rows * seq_len) + rows - 1``, safe without a length (``stream_max_segments`` of the lengths is
-    the tight one). CPU tensors take ``ref_stream_tokens`` (``table`` is not needed): the same dict."""
+    the tight one). CPU tensors take ``ref_stream_tokens`` (``table`` is not needed): the same dict.
+
+    Shuffled rows (``ref_stream_tokens``): ``row_perm``, a ``FeistelPermutation`` of the stream's full rows, gives
+    batch row ``k`` = stream row ``row_perm(row_base + k)``; ``row_index``, an int64 tensor of ``rows`` entries on
+    the corpus's device (``row_base`` 0), gives stream row ``row_index[k]``. Either launches
+    ``token_stream_plan_rows`` (two launches) in front of the same emit launch; ``out`` then holds
+    ``sum(token_stream_bytes(..., shuffled_rows=True))`` bytes and ``max_segs`` None is ``min(min(n, rows * seq_len)
+    + 2 * rows, rows * seq_len)``. ``stream_rows``: the stream's full rows ``T // seq_len``, the domain ``row_perm``
+    must have; None with ``row_perm`` on the GPU reads ``table[n]`` back, the one synchronising step here."""
     flat, offs, _ = _device_plan_args(corpus, corpus_offsets, None, None, 0, 0, seq_len, position_dtype)
     ignore_index = _label_args(labels, ignore_index)
     S, R, n = int(seq_len), int(rows), offs.numel() - 1
@@ -1485,28 +1599,59 @@ def stream_tokens_indexed_device(corpus: torch.Tensor, corpus_offsets: torch.Ten
         raise ValueError(f"{R} rows of {S} tokens overflow int32 cu_seqlens")
     if perm is not None and perm.n != n:
         raise IndexError("the permutation's domain is not the corpus")
-    M = _stream_default_segs(n, R, S) if max_segs is None else int(max_segs)
+    if row_perm is not None and row_index is not None:
+        raise ValueError("give either row_perm or row_index, not both")
+    by_rows = row_perm is not None or row_index is not None
+    M = _stream_default_segs(n, R, S, by_rows) if max_segs is None else int(max_segs)
     if M < 1 or M >= (1 << 31) - 1:
         raise ValueError("max_segs must be >= 1 and fit the plan's int32 segment ids")
     if not flat.is_cuda:
+        if row_perm is not None:
+            o = offs.numpy()
+            _check_row_perm(row_perm, int(np.maximum(np.diff(o), 0).sum()) // S if stream_rows is None
+                            else int(stream_rows), row_base, R)
         return ref_stream_tokens(flat, offs, perm=perm, row_base=row_base, rows=R, seq_len=S, pad_id=pad_id,
-                                 position_dtype=position_dtype, max_segs=M, labels=labels, ignore_index=ignore_index)
+                                 position_dtype=position_dtype, max_segs=M, labels=labels, ignore_index=ignore_index,
+                                 row_perm=row_perm, row_index=row_index)
     if (not isinstance(table, torch.Tensor) or table.dtype != torch.int64 or table.device != flat.device
             or not table.is_contiguous() or table.numel() < n + 1):
         raise ValueError("table must be a contiguous int64 tensor of n + 1 entries on the corpus's device "
                          "(token_stream_table)")
-    plan_b, batch_b = token_stream_bytes(R, S, M, position_dtype, labels)
+    if row_index is not None:
+        if not isinstance(row_index, torch.Tensor) or row_index.dtype != torch.int64:
+            raise TypeError("row_index must be an int64 tensor")
+        if row_index.device != flat.device or not row_index.is_contiguous() or row_index.numel() != R:
+            raise ValueError(f"row_index must be a contiguous tensor of {R} entries on the corpus's device")
+        if int(row_base) != 0:
+            raise ValueError("row_index selects the batch's rows itself: row_base must be 0")
+        row_selector = _index_kw(row_index.reshape(-1), None, 0)
+    elif row_perm is not None:
+        if stream_rows is None:
+            stream_rows = int(table[n].item()) // S
+        _check_row_perm(row_perm, int(stream_rows), row_base, R)
+        row_selector = _index_kw(None, row_perm, int(row_base))
+    plan_b, batch_b = token_stream_bytes(R, S, M, position_dtype, labels, by_rows)
     handle = _stream_handle(stream)
     if isinstance(stream, int):
         stream = torch.cuda.ExternalStream(stream, device=flat.device)
     with torch.cuda.stream(stream):
         buf = _token_out_buffer(out, plan_b + batch_b, flat.device)
-    return launch_stream_plan(
-        buf.data_ptr(), buf[plan_b:], corpus_ptr=flat.data_ptr(), corpus_elems=flat.numel(),
-        tok16=flat.dtype in _TOK16, corpus_offsets_ptr=offs.data_ptr(), n_corpus=n, table_ptr=table.data_ptr(),
-        selector=_index_kw(None, perm, 0) if n else _index_kw(None, None, 0), row_base=int(row_base), rows=R,
-        seq_len=S, pad_id=pad_id, max_segs=M, position_dtype=position_dtype, stream=handle, labels=labels,
-        ignore_index=ignore_index)
+    common = dict(corpus_ptr=flat.data_ptr(), corpus_elems=flat.numel(), tok16=flat.dtype in _TOK16,
+                  corpus_offsets_ptr=offs.data_ptr(), n_corpus=n, table_ptr=table.data_ptr(),
+                  selector=_index_kw(None, perm, 0) if n else _index_kw(None, None, 0), rows=R, seq_len=S,
+                  pad_id=pad_id, max_segs=M, position_dtype=position_dtype, stream=handle, labels=labels,
+                  ignore_index=ignore_index)
+    if by_rows:
+        return launch_stream_plan_rows(buf.data_ptr(), buf[plan_b:], row_selector=row_selector,
+                                       stream_rows=0 if stream_rows is None else int(stream_rows), **common)
+    return launch_stream_plan(buf.data_ptr(), buf[plan_b:], row_base=int(row_base), **common)
+
+
+def _check_row_perm(row_perm: FeistelPermutation, stream_rows: int, row_base: int, rows: int) -> None:
+    if row_perm.n != stream_rows:
+        raise IndexError(f"row_perm permutes {row_perm.n} rows, the stream has {stream_rows} full rows")
+    if int(row_base) + int(rows) > row_perm.n:
+        raise IndexError("row_perm positions out of range")
 
 
 # ----------------------------------------------------------------- reductions

@@ -60,6 +60,16 @@ def round_keys(seed: int, epoch: int) -> list[int]:
     return list(_round_keys_cached(int(seed), int(epoch)))
 
 
+_ROW_SEED_SALT = 0x726F77735F736867  # "rows_shg"
+
+
+def row_seed_for(seed: int) -> int:
+    """The seed of the token stream loader's row permutation (``shuffle_rows``), derived from the loader's
+    ``seed`` so that the rows' order is independent of the documents': ``mix64(seed ^ salt)`` reduced to 63 bits
+    (a non-negative int64, as checkpoints store it)."""
+    return _mix64_int((int(seed) ^ _ROW_SEED_SALT) & _MASK64) & ((1 << 63) - 1)
+
+
 def half_bits_for(n: int) -> int:
     if n <= 0:
         raise ValueError("permutation domain must be positive")

@@ -21,6 +21,15 @@ window's documents in it and writes the pack plan -- a segment is a maximal run 
 launches, no copy, no host read of device memory, no synchronisation per step or per epoch (two tables are
 kept, since prefetch crosses the epoch boundary; everything is ordered by the prep stream). ``ops.ref_stream_tokens``
 is the definition; with ``device="cpu"`` the loader runs it and gives the same dict.
+
+``shuffle_rows=True`` adds the sample shuffle of the format (Megatron's ``shuffle_idx``): in stream order every
+document longer than ``S`` puts all its pieces into neighbouring rows of one step. Global batch ``g`` of epoch
+``e`` is then rows ``rho_e(g * GB + j)``, ``j < GB`` (rank ``r`` takes ``j`` in ``[r * LB, (r + 1) * LB)``), with
+``rho_e = FeistelPermutation(rows_per_epoch, row_seed, e)`` and ``row_seed = permutation.row_seed_for(seed)``; the
+rows dropped at the epoch's end are a different set each epoch. The batches stay dense, static-shaped and the
+same at every world size. ``token_stream_plan_rows`` (two launches, one wave per row) takes the place of
+``token_stream_plan``, the emit launch is the same: three launches per step, and two more cached selectors per
+epoch on the host.
 """
 
 from __future__ import annotations
@@ -33,8 +42,9 @@ import torch
 from . import _native
 from .exceptions import DDLError
 from .models.tokens import SharedTokenSource
-from .ops.kernels import launch_stream_plan, ref_stream_tokens, stream_max_segments, token_stream_bytes
-from .permutation import FeistelPermutation
+from .ops.kernels import (launch_stream_plan, launch_stream_plan_rows, ref_stream_tokens, stream_max_segments,
+                          token_stream_bytes)
+from .permutation import FeistelPermutation, row_seed_for
 from .resident import STATE_VERSION, PrefetchedIndexedLoader
 from .resident_tokens import _REPLICAS, _acquire_replica, _release_replica, _replica_offsets
 from .types import DDLEnv
@@ -55,10 +65,12 @@ class ResidentTokenStreamLoader(PrefetchedIndexedLoader):
                  device: str | torch.device | None = None, n_epochs: int | None = None,
                  resume_state: dict | None = None, handoff: str = "device", hbm_fraction: float = 0.8,
                  chunk_bytes: int = 256 << 20, max_segments: int | None = None, labels: bool = False,
-                 ignore_index: int = -100):
+                 ignore_index: int = -100, shuffle_rows: bool = False):
         """``global_batch`` counts rows. ``max_segments``: the capacity of a batch's ``cu_seqlens`` (default
         ``ops.stream_max_segments``, which no window of any order exceeds; a smaller one that a batch overflows
-        gives that batch as padding with ``n_rows`` = -1)."""
+        gives that batch as padding with ``n_rows`` = -1). ``shuffle_rows``: the rows of an epoch in the order of
+        a second permutation (see the module's text); ``shuffle=False`` with it gives shuffled rows of the
+        unshuffled stream."""
         if handoff not in ("device", "host"):
             raise ValueError("handoff must be 'device' or 'host'")
         self.labels, self.ignore_index = bool(labels), int(ignore_index)
@@ -85,8 +97,10 @@ class ResidentTokenStreamLoader(PrefetchedIndexedLoader):
             raise ValueError(f"the corpus holds {self.total_tokens} tokens, fewer than one global batch of "
                              f"{self.GB} x {self.seq_len}")
         self.order = _RowOrder(self.total_tokens // self.seq_len, self.GB, int(seed), bool(shuffle))
-        self.max_segments = (stream_max_segments(lens, self.LB, self.seq_len) if max_segments is None
-                             else int(max_segments))
+        self.shuffle_rows = bool(shuffle_rows)
+        self.row_seed = row_seed_for(seed)
+        self.max_segments = (stream_max_segments(lens, self.LB, self.seq_len, self.shuffle_rows)
+                             if max_segments is None else int(max_segments))
         if self.max_segments < 1:
             raise ValueError("max_segments must be >= 1")
         self._max_seqlen = min(self.seq_len, int(source.max_len))
@@ -108,6 +122,7 @@ class ResidentTokenStreamLoader(PrefetchedIndexedLoader):
         self._kernel_evs: list = []
         self.tables_built = 0
         self._selectors: dict = {}
+        self._row_selectors: dict = {}
         self._windows: list = []
         if self.prep_stream is None:
             return
@@ -129,7 +144,8 @@ class ResidentTokenStreamLoader(PrefetchedIndexedLoader):
                 self._scratch = torch.empty(scratch, dtype=torch.int64, device=self.device)
                 self._table_epoch = [None, None]
                 self._plan_bytes, self._batch_bytes = token_stream_bytes(self.LB, self.seq_len, self.max_segments,
-                                                                         labels=self.labels)
+                                                                         labels=self.labels,
+                                                                         shuffled_rows=self.shuffle_rows)
                 self._windows = [torch.empty(self._plan_bytes, dtype=torch.uint8, device=self.device)
                                  for _ in range(self.depth + 1)]
         except Exception:
@@ -150,6 +166,19 @@ class ResidentTokenStreamLoader(PrefetchedIndexedLoader):
             sel = dict(mode=2, idx=0, base=0, **perm.device_args()) if perm is not None else dict(
                 mode=0, idx=0, base=0, keys=[0] * 6, n_domain=1, half_bits=1)
             self._selectors[epoch] = sel
+        return sel
+
+    def _row_perm(self, epoch: int) -> FeistelPermutation | None:
+        return FeistelPermutation(self.order.n_samples, self.row_seed, epoch) if self.shuffle_rows else None
+
+    def _row_selector(self, epoch: int) -> dict:
+        """The ``RowIndex`` arguments of epoch ``epoch``'s row permutation; a step sets its own ``base``."""
+        sel = self._row_selectors.get(epoch)
+        if sel is None:
+            if len(self._row_selectors) > 8:
+                self._row_selectors.clear()
+            sel = dict(mode=2, idx=0, base=0, **self._row_perm(epoch).device_args())
+            self._row_selectors[epoch] = sel
         return sel
 
     def _table(self, epoch: int, sel: dict) -> torch.Tensor:
@@ -173,7 +202,7 @@ class ResidentTokenStreamLoader(PrefetchedIndexedLoader):
         if st is None:  # the CPU twin: the definition itself
             r = ref_stream_tokens(self._toks, self._offs_t, perm=self._perm(e), row_base=row_base, rows=self.LB,
                                   seq_len=self.seq_len, pad_id=self.pad_id, max_segs=self.max_segments,
-                                  labels=self.labels, ignore_index=self.ignore_index)
+                                  labels=self.labels, ignore_index=self.ignore_index, row_perm=self._row_perm(e))
             ev = None
         else:
             timed = self.profile_every > 0 and t % self.profile_every == 0
@@ -187,12 +216,17 @@ class ResidentTokenStreamLoader(PrefetchedIndexedLoader):
                 if timed:
                     ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                     ev0.record(st)
-                r = launch_stream_plan(
-                    win.data_ptr(), whole, corpus_ptr=self._hbm.data_ptr(), corpus_elems=self.n_elems,
+                common = dict(
+                    corpus_ptr=self._hbm.data_ptr(), corpus_elems=self.n_elems,
                     tok16=self.source.token_bytes == 2, corpus_offsets_ptr=self._offs_dev.data_ptr(),
-                    n_corpus=self.n_documents, table_ptr=table.data_ptr(), selector=sel, row_base=row_base,
+                    n_corpus=self.n_documents, table_ptr=table.data_ptr(), selector=sel,
                     rows=self.LB, seq_len=self.seq_len, pad_id=self.pad_id, max_segs=self.max_segments,
                     stream=st.cuda_stream, labels=self.labels, ignore_index=self.ignore_index)
+                if self.shuffle_rows:
+                    r = launch_stream_plan_rows(win.data_ptr(), whole, stream_rows=self.order.n_samples,
+                                                row_selector=dict(self._row_selector(e), base=row_base), **common)
+                else:
+                    r = launch_stream_plan(win.data_ptr(), whole, row_base=row_base, **common)
                 if timed:
                     ev1.record(st)
                     self._kernel_evs.append((ev0, ev1))
@@ -219,6 +253,8 @@ class ResidentTokenStreamLoader(PrefetchedIndexedLoader):
             "n_documents": self.n_documents,
             "total_tokens": self.total_tokens,
             "shuffle": self.order.shuffle,
+            "shuffle_rows": self.shuffle_rows,
+            "row_seed": self.row_seed,
             "world_size": self.W,
         }
 
@@ -231,6 +267,11 @@ class ResidentTokenStreamLoader(PrefetchedIndexedLoader):
                           ("shuffle", self.order.shuffle)):
             if sd.get(key) is not None and sd[key] != mine:
                 raise ValueError(f"checkpoint {key}={sd[key]} does not match {mine}")
+        if bool(sd.get("shuffle_rows", False)) != self.shuffle_rows:  # a state without the key: contiguous rows
+            raise ValueError(f"checkpoint shuffle_rows={bool(sd.get('shuffle_rows', False))} does not match "
+                             f"{self.shuffle_rows}")
+        if self.shuffle_rows and sd.get("row_seed") != self.row_seed:
+            raise ValueError(f"checkpoint row_seed={sd.get('row_seed')} does not match {self.row_seed}")
         self.epoch, self.cursor = int(sd["epoch"]), int(sd["global_batch_cursor"])
         if self.cursor >= self.order.batches_per_epoch:
             self.epoch, self.cursor = self.epoch + 1, 0
@@ -258,7 +299,7 @@ class ResidentTokenStreamLoader(PrefetchedIndexedLoader):
                 "load_gbps": self.nbytes / self.load_s / 1e9 if self.load_s > 0 else 0.0, "handoff": self.handoff,
                 "host_waits": self.host_waits, "replica_shared": self.replica_shared, "format": "stream",
                 "rows_per_epoch": self.order.n_samples, "max_segments": self.max_segments,
-                "tables_built": self.tables_built}
+                "tables_built": self.tables_built, "shuffle_rows": self.shuffle_rows}
 
     def close(self) -> None:
         if getattr(self, "prep_stream", None) is not None:

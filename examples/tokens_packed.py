@@ -35,7 +35,9 @@ only issues launches. Packing is in-order, shapes are static (fixed rows, ``cu_s
 ``--resident --stream`` delivers the GPT pre-training format instead (``ResidentTokenStreamLoader``): the epoch's
 shuffled documents concatenated and cut every ``seq_len`` tokens, so ``--global-batch`` counts ROWS, every row is
 full (100% dense, static shapes) and a segment is a run of one document inside one row. The stream's table and
-each batch's plan are built on the GPU; the checkpoint is ``kind="token_stream"``.
+each batch's plan are built on the GPU; the checkpoint is ``kind="token_stream"``. ``--shuffle-rows`` adds the
+sample shuffle of that format (Megatron's ``shuffle_idx``): a step's rows are drawn from all over the epoch's
+stream by a second permutation, so the pieces of a long document no longer sit in neighbouring rows of one step.
 
 ``--labels`` (with ``--resident`` or ``--zero-copy``) asks the loader for the next-token targets as well
 (``labels=True``: int64 ``labels``, ``-100`` where a position has no target -- the end of a row or of a segment,
@@ -72,6 +74,8 @@ def main() -> None:
     ap.add_argument("--stream", action="store_true",
                     help="with --resident: full rows cut from the concatenated shuffled documents "
                          "(--global-batch counts rows)")
+    ap.add_argument("--shuffle-rows", action="store_true",
+                    help="with --resident --stream: the epoch's rows in a shuffled order (shuffle_rows=True)")
     ap.add_argument("--labels", action="store_true",
                     help="with --resident or --zero-copy: the loader also delivers next-token labels, and every "
                          "batch runs a tiny embedding -> linear -> cross_entropy step on them")
@@ -85,6 +89,8 @@ def main() -> None:
         ap.error("--device-plan is a mode of --resident")
     if a.stream and (not a.resident or a.device_plan or a.mode != "pack"):
         ap.error("--stream is a format of --resident (packed rows by construction; it has no --device-plan mode)")
+    if a.shuffle_rows and not a.stream:
+        ap.error("--shuffle-rows is an option of --resident --stream")
     if a.labels and not (a.zero_copy or a.resident):
         ap.error("--labels needs --resident or --zero-copy (the producer path does not deliver labels)")
     vocab = a.vocab or (512 if a.labels else 50257)
@@ -105,7 +111,8 @@ def main() -> None:
                 src = SharedTokenSource(SharedArraySource(name + "_tok", n_tok, (1,), "int32"), offs, a.seq_len)
             pack_order = "ffd" if a.mode == "pack" else "in_order"
             if a.stream:
-                dl = ddl_amd.ResidentTokenStreamLoader(src, a.global_batch, a.seq_len, env, n_epochs=a.epochs, **lab_kw)
+                dl = ddl_amd.ResidentTokenStreamLoader(src, a.global_batch, a.seq_len, env, n_epochs=a.epochs,
+                                                       shuffle_rows=a.shuffle_rows, **lab_kw)
             elif a.resident and a.device_plan:  # first-fit-decreasing is a host plan
                 dl = ddl_amd.ResidentTokenLoader(src, a.global_batch, a.seq_len, a.mode, env, n_epochs=a.epochs,
                                                  plan="device", **lab_kw)
