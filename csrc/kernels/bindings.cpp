@@ -99,6 +99,77 @@ ddl::Affine make_affine(const std::vector<float>& scale, const std::vector<float
   return a;
 }
 
+// ptrs: the groups' outputs (split_columns) or sources (pack_columns); `what` names the op in the messages
+ddl::SplitSpec make_split(const std::vector<uintptr_t>& ptrs, const std::vector<int>& widths, int out_dt,
+                          int64_t n_values, const std::string& what) {
+  if (ptrs.size() != widths.size() || ptrs.empty() || ptrs.size() > 8)
+    throw std::invalid_argument(what + ": 1..8 groups");
+  ddl::SplitSpec sp{};
+  int64_t tot = 0;
+  for (size_t i = 0; i < ptrs.size(); ++i) {
+    sp.dst[i] = as_ptr<void>(ptrs[i]);
+    sp.width[i] = widths[i];
+    tot += widths[i];
+  }
+  if (tot != n_values) throw std::invalid_argument(what + ": widths must sum to n_values");
+  sp.n_groups = static_cast<int32_t>(ptrs.size());
+  sp.out_dt = out_dt;
+  return sp;
+}
+
+// the arguments pad_pack_tokens and pad_pack_tokens_indexed share (tokens = 0 for the indexed op)
+ddl::TokenSpec make_tokens(uintptr_t tokens, uintptr_t offsets, uintptr_t row_start, uintptr_t row_end,
+                           uintptr_t seg_offsets, int64_t n_seg, uintptr_t out_tokens, uintptr_t attn_mask,
+                           uintptr_t position_ids, bool pos_is_i64, uintptr_t segment_ids, uintptr_t cu_seqlens_out,
+                           int64_t rows, int64_t seq_len, int pad_id, int mode, int64_t fill_rows,
+                           uintptr_t dev_counts, bool tok16, uintptr_t labels, int32_t ignore_index) {
+  ddl::TokenSpec sp{};
+  sp.tokens = as_ptr<const void>(tokens);
+  sp.offsets = as_ptr<const int64_t>(offsets);
+  sp.row_start = as_ptr<const int64_t>(row_start);
+  sp.row_end = as_ptr<const int64_t>(row_end);
+  sp.seg_offsets = as_ptr<const int64_t>(seg_offsets);
+  sp.n_seg = n_seg;
+  sp.out_tokens = as_ptr<int32_t>(out_tokens);
+  sp.attn_mask = as_ptr<uint8_t>(attn_mask);
+  sp.position_ids = as_ptr<void>(position_ids);
+  sp.pos_is_i64 = pos_is_i64 ? 1 : 0;
+  sp.segment_ids = as_ptr<int32_t>(segment_ids);
+  sp.cu_seqlens_out = as_ptr<int32_t>(cu_seqlens_out);
+  sp.rows = rows;
+  sp.seq_len = seq_len;
+  sp.pad_id = pad_id;
+  sp.mode = mode;
+  sp.fill_rows = fill_rows;
+  sp.dev_counts = as_ptr<const int64_t>(dev_counts);
+  sp.tok16 = tok16 ? 1 : 0;
+  sp.labels = as_ptr<int64_t>(labels);
+  sp.ignore_index = ignore_index;
+  return sp;
+}
+
+// what token_stream_plan and token_stream_plan_rows share
+ddl::StreamPlanOut make_stream_plan(uintptr_t table, uintptr_t corpus_offsets, int64_t n_corpus,
+                                    const ddl::RowIndex& ri, int64_t n, int64_t rows, int64_t seq_len,
+                                    int64_t max_segs, uintptr_t seg_offsets, uintptr_t seg_src, uintptr_t row_start,
+                                    uintptr_t row_end, uintptr_t counts) {
+  ddl::StreamPlanOut p{};
+  p.table = as_ptr<const int64_t>(table);
+  p.corpus_offsets = as_ptr<const int64_t>(corpus_offsets);
+  p.n_corpus = n_corpus;
+  p.ri = ri;
+  p.n = n;
+  p.rows = rows;
+  p.seq_len = seq_len;
+  p.max_segs = max_segs;
+  p.seg_offsets = as_ptr<int64_t>(seg_offsets);
+  p.seg_src = as_ptr<int64_t>(seg_src);
+  p.row_start = as_ptr<int64_t>(row_start);
+  p.row_end = as_ptr<int64_t>(row_end);
+  p.counts = as_ptr<int64_t>(counts);
+  return p;
+}
+
 // Host callback run by the HIP runtime once every prior op on the stream has
 // retired: hands a shm slot back to its producer (state store + futex wake).
 struct ReleaseReq {
@@ -626,18 +697,7 @@ PYBIND11_MODULE(_ddl_hip, m) {
       [](std::vector<uintptr_t> dsts, std::vector<int> widths, int out_dt, uintptr_t src, int in_dt, int64_t n_rows,
          int64_t n_values, int mode, uintptr_t idx, int64_t base, std::vector<uint64_t> keys, uint64_t n_domain,
          uint32_t half_bits, uintptr_t stream) {
-        if (dsts.size() != widths.size() || dsts.empty() || dsts.size() > 8)
-          throw std::invalid_argument("split_columns: 1..8 groups");
-        ddl::SplitSpec sp{};
-        int64_t tot = 0;
-        for (size_t i = 0; i < dsts.size(); ++i) {
-          sp.dst[i] = as_ptr<void>(dsts[i]);
-          sp.width[i] = widths[i];
-          tot += widths[i];
-        }
-        if (tot != n_values) throw std::invalid_argument("split_columns: widths must sum to n_values");
-        sp.n_groups = static_cast<int32_t>(dsts.size());
-        sp.out_dt = out_dt;
+        const ddl::SplitSpec sp = make_split(dsts, widths, out_dt, n_values, "split_columns");
         const ddl::RowIndex ri = make_index(mode, idx, base, keys, n_domain, half_bits);
         check_rc(ddl::split_columns(sp, as_ptr<const void>(src), in_dt, n_rows, n_values, ri, as_stream(stream)),
                  "split_columns");
@@ -683,18 +743,7 @@ PYBIND11_MODULE(_ddl_hip, m) {
       [](std::vector<uintptr_t> srcs, std::vector<int> widths, int in_dt, uintptr_t dst, int out_dt, int64_t n_rows,
          int64_t n_values, int mode, uintptr_t idx, int64_t base, std::vector<uint64_t> keys, uint64_t n_domain,
          uint32_t half_bits, uintptr_t stream) {
-        if (srcs.size() != widths.size() || srcs.empty() || srcs.size() > 8)
-          throw std::invalid_argument("pack_columns: 1..8 groups");
-        ddl::SplitSpec sp{};
-        int64_t tot = 0;
-        for (size_t i = 0; i < srcs.size(); ++i) {
-          sp.dst[i] = as_ptr<void>(srcs[i]);
-          sp.width[i] = widths[i];
-          tot += widths[i];
-        }
-        if (tot != n_values) throw std::invalid_argument("pack_columns: widths must sum to n_values");
-        sp.n_groups = static_cast<int32_t>(srcs.size());
-        sp.out_dt = out_dt;
+        const ddl::SplitSpec sp = make_split(srcs, widths, out_dt, n_values, "pack_columns");
         const ddl::RowIndex ri = make_index(mode, idx, base, keys, n_domain, half_bits);
         check_rc(ddl::pack_columns(sp, as_ptr<void>(dst), in_dt, n_rows, n_values, ri, as_stream(stream)),
                  "pack_columns");
@@ -709,28 +758,10 @@ PYBIND11_MODULE(_ddl_hip, m) {
          uintptr_t segment_ids, uintptr_t cu_seqlens_out, int64_t rows, int64_t seq_len, int pad_id, int mode,
          uintptr_t stream, int64_t fill_rows, uintptr_t dev_counts, bool tok16, uintptr_t labels,
          int32_t ignore_index) {
-        ddl::TokenSpec sp{};
-        sp.labels = as_ptr<int64_t>(labels);
-        sp.ignore_index = ignore_index;
-        sp.tok16 = tok16 ? 1 : 0;
-        sp.fill_rows = fill_rows;
-        sp.dev_counts = as_ptr<const int64_t>(dev_counts);
-        sp.tokens = as_ptr<const void>(tokens);
-        sp.offsets = as_ptr<const int64_t>(offsets);
-        sp.row_start = as_ptr<const int64_t>(row_start);
-        sp.row_end = as_ptr<const int64_t>(row_end);
-        sp.seg_offsets = as_ptr<const int64_t>(seg_offsets);
-        sp.n_seg = n_seg;
-        sp.out_tokens = as_ptr<int32_t>(out_tokens);
-        sp.attn_mask = as_ptr<uint8_t>(attn_mask);
-        sp.position_ids = as_ptr<void>(position_ids);
-        sp.pos_is_i64 = pos_is_i64 ? 1 : 0;
-        sp.segment_ids = as_ptr<int32_t>(segment_ids);
-        sp.cu_seqlens_out = as_ptr<int32_t>(cu_seqlens_out);
-        sp.rows = rows;
-        sp.seq_len = seq_len;
-        sp.pad_id = pad_id;
-        sp.mode = mode;
+        const ddl::TokenSpec sp =
+            make_tokens(tokens, offsets, row_start, row_end, seg_offsets, n_seg, out_tokens, attn_mask, position_ids,
+                        pos_is_i64, segment_ids, cu_seqlens_out, rows, seq_len, pad_id, mode, fill_rows, dev_counts,
+                        tok16, labels, ignore_index);
         check_rc(ddl::pad_pack_tokens(sp, as_stream(stream)), "pad_pack_tokens");
       },
       py::arg("tokens"), py::arg("offsets"), py::arg("row_start"), py::arg("row_end"), py::arg("seg_offsets"),
@@ -745,27 +776,10 @@ PYBIND11_MODULE(_ddl_hip, m) {
          uintptr_t attn_mask, uintptr_t position_ids, bool pos_is_i64, uintptr_t segment_ids, uintptr_t cu_seqlens_out,
          int64_t rows, int64_t seq_len, int pad_id, int mode, uintptr_t stream, int64_t fill_rows, bool tok16,
          uintptr_t dev_counts, int64_t cu_cap, uintptr_t labels, int32_t ignore_index) {
-        ddl::TokenSpec sp{};
-        sp.labels = as_ptr<int64_t>(labels);
-        sp.ignore_index = ignore_index;
-        sp.tok16 = tok16 ? 1 : 0;
-        sp.fill_rows = fill_rows;
-        sp.dev_counts = as_ptr<const int64_t>(dev_counts);
-        sp.offsets = as_ptr<const int64_t>(offsets);
-        sp.row_start = as_ptr<const int64_t>(row_start);
-        sp.row_end = as_ptr<const int64_t>(row_end);
-        sp.seg_offsets = as_ptr<const int64_t>(seg_offsets);
-        sp.n_seg = n_seg;
-        sp.out_tokens = as_ptr<int32_t>(out_tokens);
-        sp.attn_mask = as_ptr<uint8_t>(attn_mask);
-        sp.position_ids = as_ptr<void>(position_ids);
-        sp.pos_is_i64 = pos_is_i64 ? 1 : 0;
-        sp.segment_ids = as_ptr<int32_t>(segment_ids);
-        sp.cu_seqlens_out = as_ptr<int32_t>(cu_seqlens_out);
-        sp.rows = rows;
-        sp.seq_len = seq_len;
-        sp.pad_id = pad_id;
-        sp.mode = mode;
+        const ddl::TokenSpec sp =
+            make_tokens(0, offsets, row_start, row_end, seg_offsets, n_seg, out_tokens, attn_mask, position_ids,
+                        pos_is_i64, segment_ids, cu_seqlens_out, rows, seq_len, pad_id, mode, fill_rows, dev_counts,
+                        tok16, labels, ignore_index);
         check_rc(ddl::pad_pack_tokens_indexed(sp, as_ptr<const void>(corpus), corpus_elems,
                                               as_ptr<const int64_t>(src_start), as_ptr<const int64_t>(seg_src),
                                               as_stream(stream), cu_cap),
@@ -824,20 +838,10 @@ PYBIND11_MODULE(_ddl_hip, m) {
          int64_t seq_len, int64_t max_segs, uintptr_t seg_offsets, uintptr_t seg_src, uintptr_t row_start,
          uintptr_t row_end, uintptr_t counts, uintptr_t stream) {
         ddl::StreamPlanSpec sp{};
-        sp.table = as_ptr<const int64_t>(table);
-        sp.corpus_offsets = as_ptr<const int64_t>(corpus_offsets);
-        sp.n_corpus = n_corpus;
-        sp.ri = make_index(mode, idx, base, keys, n_domain, half_bits);
-        sp.n = n;
+        const ddl::RowIndex ri = make_index(mode, idx, base, keys, n_domain, half_bits);
+        sp.p = make_stream_plan(table, corpus_offsets, n_corpus, ri, n, rows, seq_len, max_segs, seg_offsets, seg_src,
+                                row_start, row_end, counts);
         sp.row_base = row_base;
-        sp.rows = rows;
-        sp.seq_len = seq_len;
-        sp.max_segs = max_segs;
-        sp.seg_offsets = as_ptr<int64_t>(seg_offsets);
-        sp.seg_src = as_ptr<int64_t>(seg_src);
-        sp.row_start = as_ptr<int64_t>(row_start);
-        sp.row_end = as_ptr<int64_t>(row_end);
-        sp.counts = as_ptr<int64_t>(counts);
         check_rc(ddl::token_stream_plan(sp, as_stream(stream)), "token_stream_plan");
       },
       py::arg("table"), py::arg("corpus_offsets"), py::arg("n_corpus"), py::arg("mode"), py::arg("idx"),
@@ -853,21 +857,11 @@ PYBIND11_MODULE(_ddl_hip, m) {
          uintptr_t seg_offsets, uintptr_t seg_src, uintptr_t row_start, uintptr_t row_end, uintptr_t counts,
          uintptr_t scratch, uintptr_t stream) {
         ddl::StreamRowsSpec sp{};
-        sp.table = as_ptr<const int64_t>(table);
-        sp.corpus_offsets = as_ptr<const int64_t>(corpus_offsets);
-        sp.n_corpus = n_corpus;
-        sp.ri = make_index(mode, idx, base, keys, n_domain, half_bits);
-        sp.n = n;
+        const ddl::RowIndex ri = make_index(mode, idx, base, keys, n_domain, half_bits);
+        sp.p = make_stream_plan(table, corpus_offsets, n_corpus, ri, n, rows, seq_len, max_segs, seg_offsets, seg_src,
+                                row_start, row_end, counts);
         sp.rows_ri = make_index(rows_mode, rows_idx, rows_base, rows_keys, rows_n_domain, rows_half_bits);
         sp.stream_rows = stream_rows;
-        sp.rows = rows;
-        sp.seq_len = seq_len;
-        sp.max_segs = max_segs;
-        sp.seg_offsets = as_ptr<int64_t>(seg_offsets);
-        sp.seg_src = as_ptr<int64_t>(seg_src);
-        sp.row_start = as_ptr<int64_t>(row_start);
-        sp.row_end = as_ptr<int64_t>(row_end);
-        sp.counts = as_ptr<int64_t>(counts);
         sp.scratch = as_ptr<int64_t>(scratch);
         check_rc(ddl::token_stream_plan_rows(sp, as_stream(stream)), "token_stream_plan_rows");
       },

@@ -64,6 +64,22 @@ DDL_HD int64_t source_row(const RowIndex& ri, int64_t r) {
   return ri.base + r;
 }
 
+// Host check every launcher that evaluates source_row(ri, 0 .. n) on the device makes first: a known mode, an index
+// vector in mode 1, no negative position, and in mode 2 every position inside the permutation's domain and the
+// domain inside the network's -- the cycle walk of feistel_perm terminates only on a bijection.
+inline bool row_index_ok(const RowIndex& ri, int64_t n) {
+  if (ri.mode < 0 || ri.mode > 2) return false;
+  if (ri.mode == 1 && n > 0 && !ri.idx) return false;
+  if (ri.mode != 1 && ri.base < 0) return false;
+  if (ri.mode == 2) {
+    const FeistelKeys& f = ri.keys;
+    if (f.n == 0 || f.half_bits < 1 || f.half_bits > 32) return false;
+    if (f.half_bits < 32 && f.n > (uint64_t{1} << (2 * f.half_bits))) return false;
+    if (static_cast<uint64_t>(ri.base) + static_cast<uint64_t>(n) > f.n) return false;
+  }
+  return true;
+}
+
 // Per-channel affine epilogue (normalisation) fused into gathers / casts:
 // out = in * scale[ch] + bias[ch], ch = (element_in_row / plane) % channels.
 constexpr int kMaxAffineChannels = 16;

@@ -193,20 +193,19 @@ struct StreamTableSpec {
 };
 int64_t token_stream_table_scratch(int64_t n);
 int token_stream_table(const StreamTableSpec& spec, hipStream_t st);
-// token_stream_plan (one workgroup): the pack plan of rows [row_base, row_base + rows) of the stream, i.e. of
-// the window [T0, T1) = [row_base * seq_len, min((row_base + rows) * seq_len, table[n])), as
-// pad_pack_tokens_indexed takes it in pack mode with dev_counts = counts, fill_rows = rows, cu_cap = max_segs. A
-// segment is a maximal run of one document inside one row: seg_offsets[k] = its start - T0 (entry n_seg = the
-// window's tokens), seg_src[k] = the corpus element of its first token; row_start / row_end [rows] = the rows'
-// limits clamped to the window's tokens; counts = {rows holding a token, n_seg, tokens, longest segment}, counts[0]
-// = -1 when n_seg > max_segs (nothing is written past the capacity; pad_pack_tokens_indexed then writes padding).
-struct StreamPlanSpec {
+// What both stream plans read and write. Either turns `rows` rows of seq_len tokens of the stream into the pack plan
+// pad_pack_tokens_indexed takes in pack mode with dev_counts = counts, fill_rows = rows, cu_cap = max_segs. A segment
+// is a maximal run of one document inside one row, numbered row-major over the batch's rows: seg_offsets[k] = its
+// first token's position in the batch (entry n_seg = the batch's tokens), seg_src[k] = the corpus element of that
+// token; row_start / row_end [rows] = the rows' limits in the batch; counts = {rows or -1, n_seg, tokens, longest
+// segment}. counts[0] = -1 marks a plan that cannot be rendered, n_seg > max_segs among them: nothing is written
+// past the capacity, and pad_pack_tokens_indexed then writes padding.
+struct StreamPlanOut {
   const int64_t* table;           // [n + 1], token_stream_table of the same ri and n
   const int64_t* corpus_offsets;  // [n_corpus + 1], device
   int64_t n_corpus;
-  RowIndex ri;
+  RowIndex ri;  // the documents' order
   int64_t n;
-  int64_t row_base;
   int64_t rows;
   int64_t seq_len;
   int64_t max_segs;      // seg_offsets holds max_segs + 1 entries, seg_src max_segs
@@ -216,6 +215,21 @@ struct StreamPlanSpec {
   int64_t* row_end;      // out: [rows]
   int64_t* counts;       // out: [4]
 };
+// the argument checks both launchers make before their own (a failure is the argument error -2)
+inline bool ts_plan_args_ok(const StreamPlanOut& p) {
+  if (p.n < 0 || p.n_corpus < 0 || p.seq_len <= 0 || p.rows < 1 || p.max_segs < 1) return false;
+  if (!p.table || !p.seg_offsets || !p.seg_src || !p.row_start || !p.row_end || !p.counts) return false;
+  if (p.n_corpus > 0 && !p.corpus_offsets) return false;
+  if (p.rows > 0x7FFFFFFF / p.seq_len) return false;  // a batch's positions fit the int32 cu_seqlens
+  return row_index_ok(p.ri, p.n);
+}
+// token_stream_plan (one workgroup): rows [row_base, row_base + rows) of the stream, i.e. the window [T0, T1) =
+// [row_base * seq_len, min((row_base + rows) * seq_len, table[n])). Segment starts are relative to T0, the rows'
+// limits are clamped to the window's tokens, counts[0] = the rows holding a token.
+struct StreamPlanSpec {
+  StreamPlanOut p;
+  int64_t row_base;
+};
 int token_stream_plan(const StreamPlanSpec& spec, hipStream_t st);
 
 // tokens_stream_rows.hip ----------------------------------------------------
@@ -223,31 +237,15 @@ int token_stream_plan(const StreamPlanSpec& spec, hipStream_t st);
 // k) (mode 0: base + k; mode 1: a device index of `rows` entries, repeats allowed; mode 2: a Feistel permutation of
 // [0, stream_rows) at position base + k), i.e. the window [rho_k * seq_len, (rho_k + 1) * seq_len). Two launches on
 // `st` of ceil(rows / 16) workgroups, one wave per row (the rows' documents counted, then the plan written behind
-// a per-workgroup reduction of the counts): no atomics, no waiting between workgroups. Writes the plan arrays of
-// token_stream_plan in the same layout, so pad_pack_tokens_indexed is called as for it: segments numbered
-// row-major over the batch's rows, row_start / row_end [k] = k * seq_len, (k + 1) * seq_len, counts = {rows, n_seg,
-// rows * seq_len, longest segment}. Only full rows can be selected: rho_k < 0 or (rho_k + 1) * seq_len > table[n]
-// makes the batch invalid -- counts[0] = -1 and counts[1 .. 3] taken over the valid rows, seg_offsets[0] = 0 and
-// no other segment entry written -- as does n_seg > max_segs (nothing written past the capacity).
-// stream_rows: the full rows of the stream as the host knows them, the domain a mode 2 rows_ri must have.
-// scratch: 4 * rows int64 of device memory between the two launches.
+// a per-workgroup reduction of the counts): no atomics, no waiting between workgroups. row_start / row_end [k] =
+// k * seq_len, (k + 1) * seq_len, counts = {rows, n_seg, rows * seq_len, longest segment}. Only full rows can be
+// selected: rho_k < 0 or (rho_k + 1) * seq_len > table[n] makes the batch invalid -- counts[0] = -1 and
+// counts[1 .. 3] taken over the valid rows, seg_offsets[0] = 0 and no other segment entry written.
 struct StreamRowsSpec {
-  const int64_t* table;           // [n + 1], token_stream_table of the same ri and n
-  const int64_t* corpus_offsets;  // [n_corpus + 1], device
-  int64_t n_corpus;
-  RowIndex ri;       // the documents' order
-  int64_t n;
-  RowIndex rows_ri;  // the rows' selection
-  int64_t stream_rows;
-  int64_t rows;
-  int64_t seq_len;
-  int64_t max_segs;      // seg_offsets holds max_segs + 1 entries, seg_src max_segs
-  int64_t* seg_offsets;  // out
-  int64_t* seg_src;      // out
-  int64_t* row_start;    // out: [rows]
-  int64_t* row_end;      // out: [rows]
-  int64_t* counts;       // out: [4]
-  int64_t* scratch;      // [4 * rows]
+  StreamPlanOut p;
+  RowIndex rows_ri;     // the rows' selection
+  int64_t stream_rows;  // the full rows of the stream as the host knows them, the domain a mode 2 rows_ri must have
+  int64_t* scratch;     // [4 * rows] int64 of device memory between the two launches
 };
 int token_stream_plan_rows(const StreamRowsSpec& spec, hipStream_t st);
 

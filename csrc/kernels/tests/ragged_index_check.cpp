@@ -5,22 +5,17 @@
 // dst_offsets[n] elements, so a unit outside the hulls or an element outside the destination is a heap
 // overflow. The result is compared with a plain per-sequence memcpy, and every destination element must
 // be written exactly once.
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
 #include <string.h>
 
-#include <vector>
-
 #include "../ragged_index.h"
+#include "check_common.h"
 
 namespace {
-
-int g_failures = 0;
 
 template <typename T>
 void run_case(const char* name, const std::vector<int64_t>& lens, const std::vector<int64_t>& idx, int shift,
               int64_t max_blocks) {
+  ++g_cases;
   constexpr int eb = static_cast<int>(sizeof(T));
   constexpr int per_unit = ddl::kRgUnitBytes / eb;
   std::vector<int64_t> offs(lens.size() + 1, 0);
@@ -69,10 +64,7 @@ void run_case(const char* name, const std::vector<int64_t>& lens, const std::vec
           const int64_t u = ddl::rg_unit(chunk, k, tid);
           if (u < units) {
             const uint64_t ua = ddl::rg_unit_addr(a, u);
-            if (ua % 16) {
-              printf("%s: unaligned unit\n", name);
-              ++g_failures;
-            }
+            if (ua % 16) fail(name, "unaligned unit");
             memcpy(v[k], reinterpret_cast<const void*>(ua), 16);  // the whole unit, as the lane's load
           }
         }
@@ -129,12 +121,7 @@ void run_all() {
   // sequences of several tiles (a tile is 16 KB of source)
   run_case<T>("long", {3, 20000, 5, 8192, 4096}, {1, 3, 4, 1}, 1, 4);
   // more sequences than the LDS cap of the tile map holds, short ones
-  std::vector<int64_t> many, many_idx;
-  for (int64_t i = 0; i < 5000; ++i) {
-    many.push_back(i % 13);
-    many_idx.push_back((i * 7) % 5000);
-  }
-  run_case<T>("many", many, many_idx, 0, 4);
+  run_case<T>("many", mod_lens(5000, 13), stride_order(5000, 7, 0, 5000), 0, 4);
   run_case<T>("n = 0", {4, 5}, {}, 0, 0);
   run_case<T>("all empty", {0, 0, 3}, {0, 1, 0}, 0, 1);
 }
@@ -144,10 +131,5 @@ void run_all() {
 int main() {
   run_all<uint16_t>();
   run_all<uint32_t>();
-  if (g_failures) {
-    printf("ragged index check: %d failures\n", g_failures);
-    return 1;
-  }
-  printf("ragged index check ok\n");
-  return 0;
+  return finish("ragged index check");
 }

@@ -7,68 +7,24 @@
 // label must be written exactly once, and the labels are compared with the definition applied by brute force to
 // the batch a plain loop builds from the explicit flat stream. A corrupt descriptor (elements outside the corpus)
 // must not be dereferenced, and its labels must still be the shifted ids the replay wrote.
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
 #include <string.h>
 
-#include <vector>
-
 #include "../tokens_indexed.h"
+#include "check_common.h"
 
 namespace {
 
-int g_failures = 0;
 int64_t g_fifth_loads = 0;  // label loads of the token at p0 + 4
 
-void fail(const char* name, const char* what) {
-  printf("%s: %s\n", name, what);
-  ++g_failures;
-}
-
-template <typename T>
-T* exact(size_t n) {  // exactly n elements (n = 0: a one-byte block nothing may touch as a T)
-  return static_cast<T*>(malloc(n ? n * sizeof(T) : 1));
-}
-
-uint64_t g_rng = 0x9E3779B97F4A7C15ull;
-int64_t rnd(int64_t n) {  // [0, n)
-  g_rng = g_rng * 6364136223846793005ull + 1442695040888963407ull;
-  return static_cast<int64_t>((g_rng >> 33) % static_cast<uint64_t>(n));
-}
-
-// the host plan (runtime/arena.cpp pack_plan): over-long sequences become S-chunks, a row breaks where the next
-// segment does not fit
-void plan(const std::vector<int64_t>& offs, int64_t S, std::vector<int64_t>* rs, std::vector<int64_t>* re,
-          std::vector<int64_t>* so) {
-  int64_t cur_s = -1, cur_e = -1, last = 0;
-  auto add = [&](int64_t s, int64_t e) {
-    so->push_back(s);
-    last = e;
-    if (cur_s < 0) {
-      cur_s = s, cur_e = e;
-    } else if (e - cur_s <= S && s == cur_e) {
-      cur_e = e;
-    } else {
-      rs->push_back(cur_s), re->push_back(cur_e);
-      cur_s = s, cur_e = e;
-    }
-  };
-  for (size_t i = 0; i + 1 < offs.size(); ++i) {
-    int64_t s = offs[i];
-    const int64_t e = offs[i + 1];
-    for (; e - s > S; s += S) add(s, s + S);
-    if (e > s) add(s, e);
-  }
-  if (cur_s >= 0) rs->push_back(cur_s), re->push_back(cur_e);
-  so->push_back(last);
-}
+Lcg g_rng{0x9E3779B97F4A7C15ull};
+int64_t rnd(int64_t n) { return g_rng.next() % n; }  // [0, n)
 
 // corrupt: 0 none; 1: every descriptor element moved so that the batch's reads straddle the corpus's end;
 // 2: far outside (negative and beyond)
 template <typename T>
 void run_case(const char* name, const std::vector<int64_t>& lens, const std::vector<int64_t>& idx, int64_t S, int mode,
               int64_t fill_rows, int corrupt = 0) {
+  ++g_cases;
   const int32_t pad_id = -7, ignore = -100;
   std::vector<int64_t> coffs(lens.size() + 1, 0);
   for (size_t i = 0; i < lens.size(); ++i) coffs[i + 1] = coffs[i] + lens[i];
@@ -90,7 +46,7 @@ void run_case(const char* name, const std::vector<int64_t>& lens, const std::vec
     for (int64_t p = 0; p < lens[idx[i]]; ++p) flat.push_back(static_cast<int64_t>(corpus[src_start[i] + p]));
   }
   std::vector<int64_t> rs_v, re_v, so_v;
-  if (mode == 1) plan(offs_v, S, &rs_v, &re_v, &so_v);
+  if (mode == 1) host_pack_plan(offs_v, S, &rs_v, &re_v, &so_v);
   const int64_t n_seg = mode == 1 ? static_cast<int64_t>(so_v.size()) - 1 : 0;
   const int64_t rows = mode == 1 ? static_cast<int64_t>(rs_v.size()) : n;
   int64_t* offsets = exact<int64_t>(n + 1);
@@ -300,10 +256,7 @@ int main() {
   run_all<uint16_t>();
   run_all<int32_t>();
   if (g_fifth_loads == 0) fail("token labels check", "no lane ever loaded the token at p0 + 4");
-  if (g_failures) {
-    printf("token labels check: %d failures\n", g_failures);
-    return 1;
-  }
-  printf("token labels check ok (%lld fifth-token loads)\n", (long long)g_fifth_loads);
-  return 0;
+  char note[64];
+  snprintf(note, sizeof note, " (%lld fifth-token loads)", (long long)g_fifth_loads);
+  return finish("token labels check", note);
 }

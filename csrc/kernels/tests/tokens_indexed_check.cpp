@@ -5,59 +5,17 @@
 // entry past its array or a store outside an output [R, S] is a heap overflow. A read inside the corpus but
 // outside the selected sequences is counted as a failure, every output element must be written exactly once,
 // and the result is compared with a plain loop over the explicitly built flat stream.
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
 #include <string.h>
 
-#include <vector>
-
 #include "../tokens_indexed.h"
+#include "check_common.h"
 
 namespace {
-
-int g_failures = 0;
-
-void fail(const char* name, const char* what) {
-  printf("%s: %s\n", name, what);
-  ++g_failures;
-}
-
-template <typename T>
-T* exact(size_t n) {  // exactly n elements (n = 0: a one-byte block nothing may touch as a T)
-  return static_cast<T*>(malloc(n ? n * sizeof(T) : 1));
-}
-
-// the host plan (runtime/arena.cpp pack_plan): over-long sequences become S-chunks, a row breaks where the next
-// segment does not fit
-void plan(const std::vector<int64_t>& offs, int64_t S, std::vector<int64_t>* rs, std::vector<int64_t>* re,
-          std::vector<int64_t>* so) {
-  int64_t cur_s = -1, cur_e = -1, last = 0;
-  auto add = [&](int64_t s, int64_t e) {
-    so->push_back(s);
-    last = e;
-    if (cur_s < 0) {
-      cur_s = s, cur_e = e;
-    } else if (e - cur_s <= S && s == cur_e) {
-      cur_e = e;
-    } else {
-      rs->push_back(cur_s), re->push_back(cur_e);
-      cur_s = s, cur_e = e;
-    }
-  };
-  for (size_t i = 0; i + 1 < offs.size(); ++i) {
-    int64_t s = offs[i];
-    const int64_t e = offs[i + 1];
-    for (; e - s > S; s += S) add(s, s + S);
-    if (e > s) add(s, e);
-  }
-  if (cur_s >= 0) rs->push_back(cur_s), re->push_back(cur_e);
-  so->push_back(last);
-}
 
 template <typename T, typename P>
 void run_case(const char* name, const std::vector<int64_t>& lens, const std::vector<int64_t>& idx, int64_t S, int mode,
               int64_t fill_rows) {
+  ++g_cases;
   const int32_t pad_id = -7;
   std::vector<int64_t> coffs(lens.size() + 1, 0);
   for (size_t i = 0; i < lens.size(); ++i) coffs[i + 1] = coffs[i] + lens[i];
@@ -78,7 +36,7 @@ void run_case(const char* name, const std::vector<int64_t>& lens, const std::vec
     }
   }
   std::vector<int64_t> rs_v, re_v, so_v;
-  if (mode == 1) plan(offs_v, S, &rs_v, &re_v, &so_v);
+  if (mode == 1) host_pack_plan(offs_v, S, &rs_v, &re_v, &so_v);
   const int64_t n_seg = mode == 1 ? static_cast<int64_t>(so_v.size()) - 1 : 0;
   const int64_t rows = mode == 1 ? static_cast<int64_t>(rs_v.size()) : n;
   // exact-size descriptor arrays, as the op uploads them
@@ -244,11 +202,7 @@ void run_all() {
   run_case<T, int64_t>("ragged, padding rows", lens, idx, 256, 1, 40);
   run_case<T, int64_t>("ragged, fewer fill rows than rows", lens, idx, 6, 1, 3);
   // plans around the LDS cap of the segment search
-  std::vector<int64_t> many, many_idx;
-  for (int64_t i = 0; i < 1100; ++i) {
-    many.push_back(i % 13);
-    many_idx.push_back((i * 7) % 1100);
-  }
+  std::vector<int64_t> many = mod_lens(1100, 13), many_idx = stride_order(1100, 7, 0, 1100);
   run_case<T, int64_t>("many", many, many_idx, 37, 1, 0);  // 1015 segments: just under the cap
   run_case<T, int64_t>("many, pad", many, many_idx, 37, 0, 0);
   run_case<T, int64_t>("many, short rows", many, many_idx, 6, 1, 0);  // ~1520 segments: searched in global memory
@@ -276,10 +230,5 @@ void run_all() {
 int main() {
   run_all<uint16_t>();
   run_all<int32_t>();
-  if (g_failures) {
-    printf("tokens indexed check: %d failures\n", g_failures);
-    return 1;
-  }
-  printf("tokens indexed check ok\n");
-  return 0;
+  return finish("tokens indexed check");
 }

@@ -5,31 +5,15 @@
 // segment written past the capacity, is a heap overflow. Every read and write index is checked against the
 // sizes as well, every output element must be written exactly once, and the result is compared with a plain
 // serial loop. The wave scan is the serial prefix sum of the wave's 64 lanes (what the __shfl_up ladder gives).
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-
-#include <vector>
-
 #include "../tokens_plan.h"
+#include "check_common.h"
 
 namespace {
-
-int g_failures = 0;
-
-void fail(const char* name, const char* what) {
-  printf("%s: %s\n", name, what);
-  ++g_failures;
-}
-
-template <typename T>
-T* exact(size_t n) {  // exactly n elements (n = 0: a one-byte block nothing may touch as a T)
-  return static_cast<T*>(malloc(n ? n * sizeof(T) : 1));
-}
 
 // lens: the corpus; idx: the selected sequences (any value: out-of-range ones are empty sequences)
 void run_case(const char* name, const std::vector<int64_t>& lens, const std::vector<int64_t>& idx, int64_t S,
               int64_t max_segs) {
+  ++g_cases;
   const int64_t n_corpus = static_cast<int64_t>(lens.size());
   const int64_t n = static_cast<int64_t>(idx.size());
   int64_t* coffs = exact<int64_t>(n_corpus + 1);
@@ -132,14 +116,10 @@ void run_case(const char* name, const std::vector<int64_t>& lens, const std::vec
 
 void run_all() {
   // the corpus of the GPU tests: lengths i % 13 (every 13th sequence is empty)
-  std::vector<int64_t> lens13, lens41;
-  for (int64_t i = 0; i < 3001; ++i) {
-    lens13.push_back(i % 13);
-    lens41.push_back(i % 41);  // up to 40 tokens: 7 segments at S = 6
-  }
+  const std::vector<int64_t> lens13 = mod_lens(3001, 13);
+  const std::vector<int64_t> lens41 = mod_lens(3001, 41);  // up to 40 tokens: 7 segments at S = 6
   for (int64_t n : {0, 1, 63, 64, 65, 1023, 1024, 1025, 2049}) {  // wave and tile edges, the carry across tiles
-    std::vector<int64_t> idx;
-    for (int64_t i = 0; i < n; ++i) idx.push_back((i * 7 + 5) % 3001);
+    const std::vector<int64_t> idx = stride_order(n, 7, 5, 3001);
     run_case("i % 13", lens13, idx, 37, 2 * n + 1);
     run_case("i % 13, short rows", lens13, idx, 6, 2 * n + 1);
     run_case("i % 41, many segments", lens41, idx, 6, 7 * n + 1);
@@ -147,9 +127,7 @@ void run_all() {
     run_case("i % 41, capacity exceeded", lens41, idx, 6, n);      // segments > max_segs: clipped
     run_case("i % 41, no capacity", lens41, idx, 6, 0);
   }
-  std::vector<int64_t> empty(50, 0), all;
-  for (int64_t i = 0; i < 1100; ++i) all.push_back(i % 50);
-  run_case("all empty", empty, all, 16, 8);
+  run_case("all empty", std::vector<int64_t>(50, 0), mod_lens(1100, 50), 16, 8);
   // indices outside the corpus are never dereferenced
   std::vector<int64_t> bad = {3, -1, 3001, 7, INT64_MIN, INT64_MAX, 3000, 0, -3001, 1 << 20};
   run_case("out-of-range indices", lens41, bad, 6, 64);
@@ -167,10 +145,5 @@ void run_all() {
 
 int main() {
   run_all();
-  if (g_failures) {
-    printf("tokens plan check: %d failures\n", g_failures);
-    return 1;
-  }
-  printf("tokens plan check ok\n");
-  return 0;
+  return finish("tokens plan check");
 }

@@ -4,44 +4,13 @@
 // and every plan array are heap buffers of exactly their size, so an offset read for an index outside the corpus,
 // a probe past the table or a segment written past the capacity is a heap overflow. Every write index is checked
 // against the sizes as well, every output element must be written exactly once, and the results are compared
-// with plain serial loops. The wave scan is the serial prefix sum of the wave's 64 lanes (what the __shfl_up
-// ladder gives); the ballot of the search is the count of the wave's lanes whose probe holds.
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-
-#include <vector>
-
-#include "../tokens_stream.h"
+// with plain serial loops. A lane's own work -- its document's length, its document clipped to the window and
+// counted -- is the kernels' source (ts_doc_len, ts_plan_doc), reading through views that name an index outside a
+// buffer. Only the wave collectives are stood in for: the wave scan is the serial prefix sum of the wave's 64 lanes
+// (what the __shfl_up ladder gives); the ballot of the search is the count of the wave's lanes whose probe holds.
+#include "stream_check_common.h"
 
 namespace {
-
-int g_failures = 0;
-
-void fail(const char* name, const char* what) {
-  printf("%s: %s\n", name, what);
-  ++g_failures;
-}
-
-template <typename T>
-T* exact(size_t n) {  // exactly n elements (n = 0: a one-byte block nothing may touch as a T)
-  return static_cast<T*>(malloc(n ? n * sizeof(T) : 1));
-}
-
-struct Corpus {
-  int64_t n_corpus;
-  int64_t* coffs;  // [n_corpus + 1]
-  int64_t n;
-  int64_t* order;  // [n]: any value (out-of-range ones are empty documents)
-};
-
-int64_t doc_len(const Corpus& c, int64_t i, const char* name) {  // ts_doc_len
-  if (i >= c.n) return 0;
-  const int64_t q = c.order[i];
-  if (!ddl::tp_index_ok(q, c.n_corpus)) return 0;
-  if (q < 0 || q + 1 > c.n_corpus) fail(name, "corpus offsets read out of range");
-  return ddl::tp_len(c.coffs[q], c.coffs[q + 1]);
-}
 
 // the three passes of token_stream_table; returns table [n + 1] (exact size, caller frees)
 int64_t* replay_table(const char* name, const Corpus& c) {
@@ -54,7 +23,7 @@ int64_t* replay_table(const char* name, const Corpus& c) {
   const auto scan_tile = [&](int64_t tile) {
     for (int t = 0; t < ddl::kTpThreads; ++t) {
       const int lane = t % ddl::kTpWave, wv = t / ddl::kTpWave;
-      len[t] = doc_len(c, tile * ddl::kTpThreads + t, name);
+      len[t] = ddl::ts_doc_len(c.offs_view(), c.n_corpus, c.order_view(), n, tile * ddl::kTpThreads + t);
       incl[t] = len[t] + (lane ? incl[t - 1] : 0);
       if (lane == ddl::kTpWave - 1) wave_tot[wv] = incl[t];
     }
@@ -109,32 +78,9 @@ int64_t* replay_table(const char* name, const Corpus& c) {
   return table;
 }
 
-// ts_wave_last_le: the 64 lanes of one wave
-int64_t replay_search(const char* name, const int64_t* table, int64_t n1, int64_t v) {
-  int64_t lo = 0, hi = n1;
-  int steps = 0;
-  while (hi - lo > 1) {
-    const int64_t stride = ddl::ts_search_stride(lo, hi);
-    int k = 0;
-    for (int lane = 0; lane < ddl::kTpWave; ++lane) {
-      const int64_t p = ddl::ts_search_probe(lo, stride, lane);
-      if (p < hi) {
-        if (p < 0 || p >= n1) fail(name, "search probe outside the table");
-        if (table[p] <= v) ++k;
-      }
-    }
-    if (k < 1) k = 1;
-    ddl::ts_search_narrow(&lo, &hi, stride, k);
-    if (++steps > 64) {
-      fail(name, "search does not terminate");
-      break;
-    }
-  }
-  return lo;
-}
-
 void run_plan(const char* name, const Corpus& c, const int64_t* table, int64_t row_base, int64_t rows, int64_t S,
               int64_t max_segs) {
+  ++g_cases;
   const int64_t n = c.n;
   int64_t* seg_offsets = exact<int64_t>(max_segs + 1);
   int64_t* seg_src = exact<int64_t>(max_segs);
@@ -159,19 +105,9 @@ void run_plan(const char* name, const Corpus& c, const int64_t* table, int64_t r
     for (int64_t b = d0; b <= d1; b += ddl::kTpThreads) {
       for (int t = 0; t < ddl::kTpThreads; ++t) {
         const int lane = t % ddl::kTpWave, wv = t / ddl::kTpWave;
-        const int64_t d = b + t;
-        int64_t hi = 0, mx = 0;
-        a[t] = lo[t] = src0[t] = cc[t] = 0;
-        if (d <= d1 && d < n) {
-          const int64_t q = c.order[d];
-          a[t] = table[d];
-          if (ddl::tp_index_ok(q, c.n_corpus) && ddl::ts_clip(a[t], table[d + 1], T0, T1, &lo[t], &hi)) {
-            if (q < 0 || q >= c.n_corpus) fail(name, "corpus offsets read out of range");
-            src0[t] = c.coffs[q];
-            cc[t] = ddl::ts_pieces(lo[t], hi, S);
-            mx = ddl::ts_piece_max(lo[t], hi, S);
-          }
-        }
+        int64_t mx;
+        ddl::ts_plan_doc(c.offs_view(), c.n_corpus, c.table_view(), c.order_view(), n, b + t, d1, T0, T1, S, &a[t],
+                         &lo[t], &src0[t], &cc[t], &mx);
         incl[t] = cc[t] + (lane ? incl[t - 1] : 0);
         if (lane == 0 || mx > wave_max[wv]) wave_max[wv] = mx;
         if (lane == ddl::kTpWave - 1) wave_seg[wv] = incl[t];
@@ -252,15 +188,9 @@ void run_plan(const char* name, const Corpus& c, const int64_t* table, int64_t r
 // lens: the corpus; order: the documents of the stream. A consistent order (in range) also runs the plan over
 // windows at the start, in the middle, ending at T and reaching past it, at capacities that fit and that do not.
 void run_case(const char* name, const std::vector<int64_t>& lens, const std::vector<int64_t>& order, bool plans) {
-  Corpus c;
-  c.n_corpus = static_cast<int64_t>(lens.size());
-  c.n = static_cast<int64_t>(order.size());
-  c.coffs = exact<int64_t>(c.n_corpus + 1);
-  c.coffs[0] = 0;
-  for (int64_t i = 0; i < c.n_corpus; ++i) c.coffs[i + 1] = c.coffs[i] + lens[i];
-  c.order = exact<int64_t>(c.n);
-  for (int64_t i = 0; i < c.n; ++i) c.order[i] = order[i];
-  int64_t* table = replay_table(name, c);
+  ++g_cases;
+  Corpus c = make_corpus(name, lens, order);
+  const int64_t* table = c.table = replay_table(name, c);
   if (plans) {
     const int64_t T = table[c.n];
     for (int64_t S : {1, 4, 6, 37, 512}) {
@@ -279,28 +209,18 @@ void run_case(const char* name, const std::vector<int64_t>& lens, const std::vec
     run_plan(name, c, table, 0, T + 3, 1, T + 8);  // one token per row: as many pieces as tokens
     run_plan(name, c, table, 0, 2, T / 2 + 1, c.n + 4);  // the whole stream in two rows: every document walked
   }
-  free(table);
-  free(c.coffs);
-  free(c.order);
+  free_corpus(&c);
 }
 
 void run_all() {
-  std::vector<int64_t> lens13, lens41, ones;
-  for (int64_t i = 0; i < 3001; ++i) {
-    lens13.push_back(i % 13);  // every 13th document is empty
-    lens41.push_back(i % 41);
-    ones.push_back(1 + i % 2);
-  }
+  const std::vector<int64_t> lens13 = mod_lens(3001, 13), lens41 = mod_lens(3001, 41), ones = mod_lens(3001, 2, 1);
   for (int64_t n : {0, 1, 63, 64, 65, 1023, 1024, 1025, 2049, 3001}) {  // wave and tile edges, the carries
-    std::vector<int64_t> order;
-    for (int64_t i = 0; i < n; ++i) order.push_back((i * 7 + 5) % 3001);
+    const std::vector<int64_t> order = stride_order(n, 7, 5, 3001);
     run_case("i % 13", lens13, order, true);
     run_case("i % 41", lens41, order, n <= 1025);
     run_case("1-2 tokens", ones, order, n >= 1024);  // > 1024 documents in one window: two plan tiles
   }
-  std::vector<int64_t> empty(50, 0), all;
-  for (int64_t i = 0; i < 1100; ++i) all.push_back(i % 50);
-  run_case("all empty", empty, all, true);
+  run_case("all empty", std::vector<int64_t>(50, 0), mod_lens(1100, 50), true);
   std::vector<int64_t> edges = {0, 0, 5, 0, 0, 0, 7, 1, 0, 12, 0};  // runs of empty documents, also at both ends
   run_case("empty runs", edges, {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10}, true);
   std::vector<int64_t> longs = {5000, 0, 4096, 4097, 1};  // documents over many rows: one lane, many pieces
@@ -312,20 +232,12 @@ void run_all() {
   run_case("out-of-range indices, two tiles", lens41, bad_many, false);
   run_case("empty corpus", {}, {0, 1, -1}, false);
   // more than 1024 tiles: the carry of the middle pass (1024 * 1024 + 5 documents)
-  std::vector<int64_t> big_lens(977), big_order;
-  for (int64_t i = 0; i < 977; ++i) big_lens[i] = i % 5;
-  for (int64_t i = 0; i < 1024 * 1024 + 5; ++i) big_order.push_back((i * 31 + 7) % 977);
-  run_case("1024 * 1024 + 5 documents", big_lens, big_order, false);
+  run_case("1024 * 1024 + 5 documents", mod_lens(977, 5), stride_order(1024 * 1024 + 5, 31, 7, 977), false);
 }
 
 }  // namespace
 
 int main() {
   run_all();
-  if (g_failures) {
-    printf("tokens stream check: %d failures\n", g_failures);
-    return 1;
-  }
-  printf("tokens stream check ok\n");
-  return 0;
+  return finish("tokens stream check");
 }

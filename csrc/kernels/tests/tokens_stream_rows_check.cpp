@@ -4,74 +4,19 @@
 // order, the table, the row index, the per-row scratch and every plan array are heap buffers of exactly their
 // size, so an offset read for an index outside the corpus, a probe past the table or a segment written past the
 // capacity is a heap overflow. Every write index is checked against the sizes as well, every output element must
-// be written exactly once, and the results are compared with a plain serial construction, token by token. The
-// ballot of a step is the set of the wave's lanes whose document leaves something in the row; a wave sum is the
-// serial sum of the wave's 64 lanes.
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-
-#include <vector>
-
+// be written exactly once, and the results are compared with a plain serial construction, token by token. A
+// lane's document clipped to its row is the kernels' source (tsr_doc), reading through views that name an index
+// outside a buffer. Only the wave collectives are stood in for: the ballot of a step is the set of the wave's lanes
+// whose document leaves something in the row; a wave sum is the serial sum of the wave's 64 lanes.
 #include "../tokens_stream_rows.h"
+#include "stream_check_common.h"
 
 namespace {
 
-int g_failures = 0;
-
-void fail(const char* name, const char* what) {
-  printf("%s: %s\n", name, what);
-  ++g_failures;
-}
-
-template <typename T>
-T* exact(size_t n) {  // exactly n elements (n = 0: a one-byte block nothing may touch as a T)
-  return static_cast<T*>(malloc(n ? n * sizeof(T) : 1));
-}
-
-struct Corpus {
-  int64_t n_corpus;
-  int64_t* coffs;  // [n_corpus + 1]
-  int64_t n;
-  int64_t* order;  // [n]
-  int64_t* table;  // [n + 1]
-};
-
-// ts_wave_last_le: the 64 lanes of one wave
-int64_t replay_search(const char* name, const int64_t* table, int64_t n1, int64_t v) {
-  int64_t lo = 0, hi = n1;
-  int steps = 0;
-  while (hi - lo > 1) {
-    const int64_t stride = ddl::ts_search_stride(lo, hi);
-    int k = 0;
-    for (int lane = 0; lane < ddl::kTpWave; ++lane) {
-      const int64_t p = ddl::ts_search_probe(lo, stride, lane);
-      if (p < hi) {
-        if (p < 0 || p >= n1) fail(name, "search probe outside the table");
-        if (table[p] <= v) ++k;
-      }
-    }
-    if (k < 1) k = 1;
-    ddl::ts_search_narrow(&lo, &hi, stride, k);
-    if (++steps > 64) {
-      fail(name, "search does not terminate");
-      break;
-    }
-  }
-  return lo;
-}
-
-// tsr_doc: one lane's document clipped to its row
-bool replay_doc(const char* name, const Corpus& c, int64_t d, int64_t d1, int64_t T0, int64_t T1, int64_t* q,
-                int64_t* a, int64_t* lo, int64_t* hi) {
-  if (d > d1 || d < 0 || d >= c.n) return false;
-  *q = c.order[d];
-  *a = c.table[d];
-  return ddl::tp_index_ok(*q, c.n_corpus) && ddl::ts_clip(*a, c.table[d + 1], T0, T1, lo, hi);
-}
-
 void run_plan(const char* name, const Corpus& c, const std::vector<int64_t>& rho_in, int64_t S, int64_t max_segs) {
+  ++g_cases;
   const int64_t rows = static_cast<int64_t>(rho_in.size()), n = c.n, T = c.table[n];
+  const View table = c.table_view(), order = c.order_view();
   int64_t* rho = exact<int64_t>(rows);  // rows_ri.idx
   for (int64_t k = 0; k < rows; ++k) rho[k] = rho_in[k];
   int64_t* scratch = exact<int64_t>(ddl::tsr_scratch_words(rows));
@@ -101,7 +46,7 @@ void run_plan(const char* name, const Corpus& c, const std::vector<int64_t>& rho
         for (int64_t b = d0; b <= d1; b += ddl::kTpWave) {
           for (int lane = 0; lane < ddl::kTpWave; ++lane) {
             int64_t q, a, lo = 0, hi = 0;
-            if (replay_doc(name, c, b + lane, d1, T0, T1, &q, &a, &lo, &hi)) {
+            if (ddl::tsr_doc(table, c.n_corpus, order, n, b + lane, d1, T0, T1, &q, &a, &lo, &hi)) {
               ++segs;
               if (hi - lo > mx) mx = hi - lo;
             }
@@ -150,7 +95,7 @@ void run_plan(const char* name, const Corpus& c, const std::vector<int64_t>& rho
         int votes = 0;
         for (int lane = 0; lane < ddl::kTpWave; ++lane) {  // votes so far = the ballot's bits below the lane
           int64_t q, a, lo = 0, hi = 0;
-          if (!replay_doc(name, c, b + lane, d1, T0, T1, &q, &a, &lo, &hi)) continue;
+          if (!ddl::tsr_doc(table, c.n_corpus, order, n, b + lane, d1, T0, T1, &q, &a, &lo, &hi)) continue;
           const int64_t i = first + votes++;
           if (ddl::tp_seg_writes(i, 1, max_segs) > 0) {
             if (i < 0 || i >= max_segs) {
@@ -239,25 +184,11 @@ void run_plan(const char* name, const Corpus& c, const std::vector<int64_t>& rho
 // lens: the corpus; order: the documents of the stream (in range). Runs the plan over selections of every kind at
 // capacities that fit and that do not.
 void run_case(const char* name, const std::vector<int64_t>& lens, const std::vector<int64_t>& order) {
-  Corpus c;
-  c.n_corpus = static_cast<int64_t>(lens.size());
-  c.n = static_cast<int64_t>(order.size());
-  c.coffs = exact<int64_t>(c.n_corpus + 1);
-  c.coffs[0] = 0;
-  for (int64_t i = 0; i < c.n_corpus; ++i) c.coffs[i + 1] = c.coffs[i] + lens[i];
-  c.order = exact<int64_t>(c.n);
-  c.table = exact<int64_t>(c.n + 1);
-  c.table[0] = 0;
-  for (int64_t i = 0; i < c.n; ++i) {
-    c.order[i] = order[i];
-    c.table[i + 1] = c.table[i] + lens[order[i]];
-  }
+  ++g_cases;
+  Corpus c = make_corpus(name, lens, order);
+  serial_table(&c);
   const int64_t T = c.table[c.n];
-  uint64_t state = 0x9E3779B97F4A7C15ull + static_cast<uint64_t>(T);
-  const auto next = [&state]() {
-    state = state * 6364136223846793005ull + 1442695040888963407ull;
-    return static_cast<int64_t>(state >> 33);
-  };
+  Lcg rng{0x9E3779B97F4A7C15ull + static_cast<uint64_t>(T)};
   for (int64_t S : {1, 4, 6, 37, 512}) {
     const int64_t full = T / S;
     for (int64_t rows : {1, 3, 16, 17, 40}) {
@@ -265,7 +196,7 @@ void run_case(const char* name, const std::vector<int64_t>& lens, const std::vec
       for (int64_t k = 0; k < rows; ++k) {
         ident.push_back(full ? k % full : 0);
         rev.push_back(full ? full - 1 - k % full : 0);
-        rnd.push_back(full ? next() % full : 0);
+        rnd.push_back(full ? rng.next() % full : 0);
         rep.push_back(full ? rnd[0] : 0);
       }
       bad_neg = bad_tail = bad_far = rnd;
@@ -282,28 +213,18 @@ void run_case(const char* name, const std::vector<int64_t>& lens, const std::vec
       }
     }
   }
-  free(c.table);
-  free(c.coffs);
-  free(c.order);
+  free_corpus(&c);
 }
 
 void run_all() {
-  std::vector<int64_t> lens13, lens41, ones;
-  for (int64_t i = 0; i < 3001; ++i) {
-    lens13.push_back(i % 13);  // every 13th document is empty
-    lens41.push_back(i % 41);
-    ones.push_back(1 + i % 2);
-  }
+  const std::vector<int64_t> lens13 = mod_lens(3001, 13), lens41 = mod_lens(3001, 41), ones = mod_lens(3001, 2, 1);
   for (int64_t n : {1, 63, 64, 65, 1025, 3001}) {
-    std::vector<int64_t> order;
-    for (int64_t i = 0; i < n; ++i) order.push_back((i * 7 + 5) % 3001);
+    const std::vector<int64_t> order = stride_order(n, 7, 5, 3001);
     run_case("i % 13", lens13, order);
     run_case("i % 41", lens41, order);
     run_case("1-2 tokens", ones, order);  // hundreds of documents per row at S = 512: several steps of the walk
   }
-  std::vector<int64_t> empty(50, 0), all;
-  for (int64_t i = 0; i < 1100; ++i) all.push_back(i % 50);
-  run_case("all empty", empty, all);  // no full row: every selection is invalid
+  run_case("all empty", std::vector<int64_t>(50, 0), mod_lens(1100, 50));  // no full row: every selection is invalid
   std::vector<int64_t> gap = {3};  // a run of 200 empty documents between two documents of one row
   for (int i = 0; i < 200; ++i) gap.push_back(0);
   gap.push_back(9);
@@ -315,38 +236,19 @@ void run_all() {
   std::vector<int64_t> longs = {5000, 0, 4096, 4097, 1};  // rows wholly inside one document
   run_case("long documents", longs, {3, 1, 0, 4, 2});
   // more rows than one pass of the 1024 lanes of the reduction
-  std::vector<int64_t> order;
-  for (int64_t i = 0; i < 3001; ++i) order.push_back((i * 11 + 3) % 3001);
-  Corpus c;
-  c.n_corpus = c.n = 3001;
-  c.coffs = exact<int64_t>(3002);
-  c.order = exact<int64_t>(3001);
-  c.table = exact<int64_t>(3002);
-  c.coffs[0] = c.table[0] = 0;
-  for (int64_t i = 0; i < 3001; ++i) c.coffs[i + 1] = c.coffs[i] + lens13[i];
-  for (int64_t i = 0; i < 3001; ++i) {
-    c.order[i] = order[i];
-    c.table[i + 1] = c.table[i] + lens13[order[i]];
-  }
-  std::vector<int64_t> many;
-  for (int64_t k = 0; k < 1025; ++k) many.push_back((k * 37) % (c.table[3001] / 8));
+  Corpus c = make_corpus("1025 rows", lens13, stride_order(3001, 11, 3, 3001));
+  serial_table(&c);
+  std::vector<int64_t> many = stride_order(1025, 37, 0, c.table[3001] / 8);
   run_plan("1025 rows", c, many, 8, 1025 * 8);
   run_plan("1025 rows", c, many, 8, 1500);
   many[1024] = -5;
   run_plan("1025 rows, the last invalid", c, many, 8, 1025 * 8);
-  free(c.table);
-  free(c.coffs);
-  free(c.order);
+  free_corpus(&c);
 }
 
 }  // namespace
 
 int main() {
   run_all();
-  if (g_failures) {
-    printf("tokens stream rows check: %d failures\n", g_failures);
-    return 1;
-  }
-  printf("tokens stream rows check ok\n");
-  return 0;
+  return finish("tokens stream rows check");
 }

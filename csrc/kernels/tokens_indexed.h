@@ -2,7 +2,7 @@
 // row length, the vector-store predicate and the search serve the flat kernel (tokens.hip) and the indexed one
 // (tokens_indexed.hip) alike (their shared device half is tokens_emit.h); ti_lane4 is the indexed kernel's lane
 // loop, which csrc/kernels/tests/tokens_indexed_check.cpp replays under ASan/UBSan; ti_labels4 is its next-token
-// label arithmetic (tests/token_labels_check.cpp).
+// label arithmetic (tests/token_labels_check.cpp). Both checks share their harness, tests/check_common.h.
 // Plain inline functions: __host__ __device__ under hipcc, plain under g++ (this header includes nothing of HIP).
 //
 // The indexed kernel writes what pad_pack_tokens (tokens.hip) writes for the VIRTUAL flat stream

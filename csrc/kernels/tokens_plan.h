@@ -1,5 +1,6 @@
 // Index arithmetic of the batch descriptor kernel (tokens_plan.hip), shared with host code:
-// csrc/kernels/tests/tokens_plan_check.cpp replays the kernel's per-lane loops with it under ASan/UBSan.
+// csrc/kernels/tests/tokens_plan_check.cpp replays the kernel's per-lane loops with it under ASan/UBSan (the
+// harness of all the checks is tests/check_common.h).
 // Plain inline functions: __host__ __device__ under hipcc, plain under g++ (this header includes nothing of HIP).
 //
 // The kernel turns the n selected sequences of a corpus (sequence q = corpus elements

@@ -109,17 +109,7 @@ int token_batch_descriptor(const BatchDescSpec& spec, hipStream_t st) {
   if (!spec.src_start || !spec.offsets || !spec.counts) return -2;
   if (spec.max_segs > 0 && !spec.seg_src) return -2;
   if (spec.n_corpus > 0 && !spec.corpus_offsets) return -2;
-  const RowIndex& ri = spec.ri;
-  if (ri.mode < 0 || ri.mode > 2) return -2;
-  if (ri.mode == 1 && spec.n > 0 && !ri.idx) return -2;
-  if (ri.mode != 1 && ri.base < 0) return -2;
-  if (ri.mode == 2) {  // every position inside the permutation's domain, and the domain inside the network's: the
-                       // cycle walk of feistel_perm terminates only on a bijection
-    const FeistelKeys& f = ri.keys;
-    if (f.n == 0 || f.half_bits < 1 || f.half_bits > 32) return -2;
-    if (f.half_bits < 32 && f.n > (uint64_t{1} << (2 * f.half_bits))) return -2;
-    if (static_cast<uint64_t>(ri.base) + static_cast<uint64_t>(spec.n) > f.n) return -2;
-  }
+  if (!row_index_ok(spec.ri, spec.n)) return -2;
   hipLaunchKernelGGL(token_batch_descriptor_kernel, dim3(1), dim3(kTpThreads), 0, st, spec);
   return static_cast<int>(hipGetLastError());
 }

@@ -1,5 +1,6 @@
-// Index arithmetic of the token stream kernels (tokens_stream.hip), shared with host code:
-// csrc/kernels/tests/tokens_stream_check.cpp replays the kernels' per-lane loops with it under ASan/UBSan.
+// Index arithmetic and per-lane routines of the token stream kernels (tokens_stream.hip), shared with host code:
+// csrc/kernels/tests/tokens_stream_check.cpp runs them under ASan/UBSan inside a replay of the kernels' loops, in
+// which only the wave collectives have a host stand-in.
 // Plain inline functions: __host__ __device__ under hipcc, plain under g++ (this header includes nothing of HIP).
 //
 // The stream of an epoch is concat(document q_0, q_1, ..., q_{n-1}) in the epoch's order; document k occupies
@@ -63,6 +64,39 @@ DDL_TS_HD int64_t ts_piece_max(int64_t lo, int64_t hi, int64_t S) {
   if (c > 2) return S;
   const int64_t first = (lo / S + 1) * S - lo, last = hi - ((hi - 1) / S) * S;
   return first > last ? first : last;
+}
+
+// The per-lane routines below read memory by a computed index, so kernel and host replay compile the same text.
+// order(i) = the corpus document at position i of the order (the kernels: source_row(ri, i)); coffs and table are
+// anything indexable by int64 (the kernels: the device pointers; the replay: views that check every index).
+
+// length of document i of an order of n documents (0 past n, and for an index outside the corpus)
+template <typename Offs, typename Order>
+DDL_TS_HD int64_t ts_doc_len(const Offs& coffs, int64_t n_corpus, const Order& order, int64_t n, int64_t i) {
+  if (i >= n) return 0;
+  const int64_t q = order(i);
+  if (!tp_index_ok(q, n_corpus)) return 0;
+  return tp_len(coffs[q], coffs[q + 1]);
+}
+
+// One lane of the plan: document d <= d1 of the order clipped to the window [T0, T1). *a = its stream position,
+// *lo = where its clipped part starts, *src0 = its first corpus element, *c = its pieces and *mx = the longest.
+// *c = *mx = 0, no piece, for a document past d1 or n, outside the corpus or with nothing inside the window.
+template <typename Offs, typename Table, typename Order>
+DDL_TS_HD void ts_plan_doc(const Offs& coffs, int64_t n_corpus, const Table& table, const Order& order, int64_t n,
+                           int64_t d, int64_t d1, int64_t T0, int64_t T1, int64_t S, int64_t* a, int64_t* lo,
+                           int64_t* src0, int64_t* c, int64_t* mx) {
+  int64_t hi = 0;
+  *a = *lo = *src0 = *c = *mx = 0;
+  if (d <= d1 && d < n) {  // d1 < n for a table that ends in its total; kept so regardless
+    const int64_t q = order(d);
+    *a = table[d];
+    if (tp_index_ok(q, n_corpus) && ts_clip(*a, table[d + 1], T0, T1, lo, &hi)) {
+      *src0 = coffs[q];
+      *c = ts_pieces(*lo, hi, S);
+      *mx = ts_piece_max(*lo, hi, S);
+    }
+  }
 }
 
 // limits of row r of a window holding n_tok tokens, and its rows with at least one token

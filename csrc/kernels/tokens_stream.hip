@@ -30,20 +30,13 @@
 namespace ddl {
 namespace {
 
-// length of document i of the order (0 past n, and for an index outside the corpus)
-__device__ __forceinline__ int64_t ts_doc_len(const StreamTableSpec& sp, int64_t i) {
-  if (i >= sp.n) return 0;
-  const int64_t q = source_row(sp.ri, i);
-  if (!tp_index_ok(q, sp.n_corpus)) return 0;
-  return tp_len(sp.corpus_offsets[q], sp.corpus_offsets[q + 1]);
-}
-
 // pass 1: tile_sums[tile] = the tokens of the tile's documents
 __global__ void __launch_bounds__(kTpThreads) token_stream_tile_sums_kernel(StreamTableSpec sp) {
   __shared__ int64_t wave_tot[kTpWaves];
   const int t = threadIdx.x, lane = t & (kTpWave - 1), wv = t / kTpWave;
   const int64_t tile = blockIdx.x;
-  const int64_t incl = ts_wave_incl_scan(ts_doc_len(sp, tile * kTpThreads + t));
+  const int64_t len = ts_doc_len(sp.corpus_offsets, sp.n_corpus, TsOrder{sp.ri}, sp.n, tile * kTpThreads + t);
+  const int64_t incl = ts_wave_incl_scan(len);
   if (lane == kTpWave - 1) wave_tot[wv] = incl;
   __syncthreads();
   if (t == 0) sp.tile_sums[tile] = tp_before(wave_tot, kTpWaves, 0);
@@ -77,14 +70,26 @@ __global__ void __launch_bounds__(kTpThreads) token_stream_tile_write_kernel(Str
   const int t = threadIdx.x, lane = t & (kTpWave - 1), wv = t / kTpWave;
   const int64_t tile = blockIdx.x;
   const int64_t i = tile * kTpThreads + t;
-  const int64_t len = ts_doc_len(sp, i);
+  const int64_t len = ts_doc_len(sp.corpus_offsets, sp.n_corpus, TsOrder{sp.ri}, sp.n, i);
   const int64_t incl = ts_wave_incl_scan(len);
   if (lane == kTpWave - 1) wave_tot[wv] = incl;
   __syncthreads();
   if (i < sp.n) sp.table[i] = tp_exclusive(tp_before(wave_tot, wv, sp.tile_sums[tile]), incl, len);
 }
 
-__global__ void __launch_bounds__(kTpThreads) token_stream_plan_kernel(StreamPlanSpec sp) {
+// The plan kernel's argument: StreamPlanSpec with row_base between n and rows. With row_base behind the shared block,
+// the layout the host-side spec has, `counts` leaves the argument's last eight bytes and the kernel measured 3 us (6%)
+// slower at 2048 rows, so the launcher passes the fields in this order.
+struct StreamPlanArgs {
+  const int64_t* table;
+  const int64_t* corpus_offsets;
+  int64_t n_corpus;
+  RowIndex ri;
+  int64_t n, row_base, rows, seq_len, max_segs;
+  int64_t *seg_offsets, *seg_src, *row_start, *row_end, *counts;
+};
+
+__global__ void __launch_bounds__(kTpThreads) token_stream_plan_kernel(StreamPlanArgs sp) {
   __shared__ int64_t wave_seg[kTpWaves], wave_max[kTpWaves];
   __shared__ int64_t carry_seg, carry_max;
   const int t = threadIdx.x, lane = t & (kTpWave - 1), wv = t / kTpWave;
@@ -99,16 +104,9 @@ __global__ void __launch_bounds__(kTpThreads) token_stream_plan_kernel(StreamPla
     const int64_t d1 = ts_wave_last_le(sp.table, sp.n + 1, T1 - 1);
     for (int64_t b = d0; b <= d1; b += kTpThreads) {  // block-uniform trip count
       const int64_t d = b + t;
-      int64_t a = 0, lo = 0, hi = 0, src0 = 0, c = 0, mx = 0;
-      if (d <= d1 && d < sp.n) {  // d1 < n for a table that ends in its total; kept so regardless
-        const int64_t q = source_row(sp.ri, d);
-        a = sp.table[d];
-        if (tp_index_ok(q, sp.n_corpus) && ts_clip(a, sp.table[d + 1], T0, T1, &lo, &hi)) {
-          src0 = sp.corpus_offsets[q];
-          c = ts_pieces(lo, hi, S);
-          mx = ts_piece_max(lo, hi, S);
-        }
-      }
+      int64_t a, lo, src0, c, mx;
+      ts_plan_doc(sp.corpus_offsets, sp.n_corpus, sp.table, TsOrder{sp.ri}, sp.n, d, d1, T0, T1, S, &a,
+                  &lo, &src0, &c, &mx);
       const int64_t incl = ts_wave_incl_scan(c);
       mx = ts_wave_max(mx);
       if (lane == kTpWave - 1) {
@@ -156,7 +154,7 @@ int64_t token_stream_table_scratch(int64_t n) { return ts_tiles(n) > 0 ? ts_tile
 int token_stream_table(const StreamTableSpec& spec, hipStream_t st) {
   if (spec.n < 0 || spec.n_corpus < 0 || !spec.table || !spec.tile_sums) return -2;
   if (spec.n_corpus > 0 && !spec.corpus_offsets) return -2;
-  if (!ts_index_ok(spec.ri, spec.n)) return -2;
+  if (!row_index_ok(spec.ri, spec.n)) return -2;
   const int64_t tiles = ts_tiles(spec.n);
   if (tiles > 0x7FFFFFFF) return -4;
   const dim3 grid(static_cast<uint32_t>(tiles)), block(kTpThreads);
@@ -167,14 +165,13 @@ int token_stream_table(const StreamTableSpec& spec, hipStream_t st) {
 }
 
 int token_stream_plan(const StreamPlanSpec& spec, hipStream_t st) {
-  if (spec.n < 0 || spec.n_corpus < 0 || spec.seq_len <= 0 || spec.rows < 1 || spec.row_base < 0) return -2;
-  if (spec.max_segs < 1 || !spec.table || !spec.seg_offsets || !spec.seg_src) return -2;
-  if (!spec.row_start || !spec.row_end || !spec.counts) return -2;
-  if (spec.n_corpus > 0 && !spec.corpus_offsets) return -2;
-  if (spec.rows > 0x7FFFFFFF / spec.seq_len) return -2;  // a batch's positions fit the int32 cu_seqlens
-  if (spec.row_base > (INT64_MAX / spec.seq_len) - spec.rows) return -2;  // (row_base + rows) * S fits int64
-  if (!ts_index_ok(spec.ri, spec.n)) return -2;
-  hipLaunchKernelGGL(token_stream_plan_kernel, dim3(1), dim3(kTpThreads), 0, st, spec);
+  if (!ts_plan_args_ok(spec.p) || spec.row_base < 0) return -2;
+  if (spec.row_base > (INT64_MAX / spec.p.seq_len) - spec.p.rows) return -2;  // (row_base + rows) * S fits int64
+  const StreamPlanOut& p = spec.p;
+  const StreamPlanArgs args{p.table,    p.corpus_offsets, p.n_corpus, p.ri,          p.n,       spec.row_base,
+                            p.rows,     p.seq_len,        p.max_segs, p.seg_offsets, p.seg_src, p.row_start,
+                            p.row_end,  p.counts};
+  hipLaunchKernelGGL(token_stream_plan_kernel, dim3(1), dim3(kTpThreads), 0, st, args);
   return static_cast<int>(hipGetLastError());
 }
 

@@ -1,5 +1,6 @@
-// Index arithmetic of the shuffled-row plan of the token stream (tokens_stream_rows.hip), shared with host code:
-// csrc/kernels/tests/tokens_stream_rows_check.cpp replays both launches' per-wave loops with it under ASan/UBSan.
+// Index arithmetic and the per-lane routine of the shuffled-row plan of the token stream (tokens_stream_rows.hip),
+// shared with host code: csrc/kernels/tests/tokens_stream_rows_check.cpp runs them under ASan/UBSan inside a replay
+// of both launches' per-wave loops, in which only the wave collectives have a host stand-in.
 // Plain inline functions: __host__ __device__ under hipcc, plain under g++ (this header includes nothing of HIP).
 //
 // Batch row k is stream row rho_k (any row of the stream, in any order, repeats allowed): the window
@@ -29,6 +30,17 @@ DDL_TSR_HD int64_t tsr_scratch_words(int64_t rows) { return kTsrRowWords * rows;
 // full rows of a stream of T tokens; a selected row is valid inside [0, that)
 DDL_TSR_HD int64_t tsr_stream_rows(int64_t T, int64_t S) { return T > 0 ? T / S : 0; }
 DDL_TSR_HD bool tsr_row_valid(int64_t rho, int64_t T, int64_t S) { return rho >= 0 && rho < tsr_stream_rows(T, S); }
+
+// One lane of either launch: document d of the order clipped to the row [T0, T1), whether anything is left (d past
+// d1, outside [0, n) or with an index outside the corpus: nothing). table and order as for ts_plan_doc.
+template <typename Table, typename Order>
+DDL_TSR_HD bool tsr_doc(const Table& table, int64_t n_corpus, const Order& order, int64_t n, int64_t d, int64_t d1,
+                        int64_t T0, int64_t T1, int64_t* q, int64_t* a, int64_t* lo, int64_t* hi) {
+  if (d > d1 || d < 0 || d >= n) return false;
+  *q = order(d);
+  *a = table[d];
+  return tp_index_ok(*q, n_corpus) && ts_clip(*a, table[d + 1], T0, T1, lo, hi);
+}
 
 // a row's count word: its segments, or -1 for an invalid row (which adds nothing to the batch)
 DDL_TSR_HD int64_t tsr_count_word(bool valid, int64_t segs) { return valid ? segs : -1; }

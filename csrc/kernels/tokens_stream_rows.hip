@@ -36,31 +36,22 @@
 namespace ddl {
 namespace {
 
-// document d of the order clipped to the row [T0, T1): whether anything is left (lane-level; d past d1, outside
-// [0, n) or with an index outside the corpus: nothing)
-__device__ __forceinline__ bool tsr_doc(const StreamRowsSpec& sp, int64_t d, int64_t d1, int64_t T0, int64_t T1,
-                                        int64_t* q, int64_t* a, int64_t* lo, int64_t* hi) {
-  if (d > d1 || d < 0 || d >= sp.n) return false;
-  *q = source_row(sp.ri, d);
-  *a = sp.table[d];
-  return tp_index_ok(*q, sp.n_corpus) && ts_clip(*a, sp.table[d + 1], T0, T1, lo, hi);
-}
-
 __global__ void __launch_bounds__(kTpThreads) token_stream_rows_count_kernel(StreamRowsSpec sp) {
   const int t = threadIdx.x, lane = t & (kTpWave - 1), wv = t / kTpWave;
   const int64_t k = static_cast<int64_t>(blockIdx.x) * kTpWaves + wv;
-  if (k < sp.rows) {  // wave-uniform; this kernel has no barrier
-    const int64_t S = sp.seq_len, T = sp.table[sp.n];
+  if (k < sp.p.rows) {  // wave-uniform; this kernel has no barrier
+    const int64_t S = sp.p.seq_len, T = sp.p.table[sp.p.n];
     const int64_t rho = source_row(sp.rows_ri, k);
     const bool valid = tsr_row_valid(rho, T, S);
     int64_t segs = 0, mx = 0, d0 = 0, d1 = 0;
     if (valid) {  // wave-uniform; then T0 < table[n]: both documents exist and are not empty
       const int64_t T0 = rho * S, T1 = T0 + S;
-      d0 = ts_wave_last_le(sp.table, sp.n + 1, T0);
-      d1 = ts_wave_last_le(sp.table, sp.n + 1, T1 - 1);
+      d0 = ts_wave_last_le(sp.p.table, sp.p.n + 1, T0);
+      d1 = ts_wave_last_le(sp.p.table, sp.p.n + 1, T1 - 1);
       for (int64_t b = d0; b <= d1; b += kTpWave) {  // wave-uniform trip count
         int64_t q, a, lo = 0, hi = 0;
-        const bool has = tsr_doc(sp, b + lane, d1, T0, T1, &q, &a, &lo, &hi);
+        const bool has =
+            tsr_doc(sp.p.table, sp.p.n_corpus, TsOrder{sp.p.ri}, sp.p.n, b + lane, d1, T0, T1, &q, &a, &lo, &hi);
         segs += __popcll(__ballot(has));
         if (has && hi - lo > mx) mx = hi - lo;
       }
@@ -69,9 +60,9 @@ __global__ void __launch_bounds__(kTpThreads) token_stream_rows_count_kernel(Str
     if (lane == 0) {
       int64_t* w = sp.scratch + k;
       w[0] = tsr_count_word(valid, segs);
-      w[sp.rows] = mx;
-      w[2 * sp.rows] = d0;
-      w[3 * sp.rows] = d1;
+      w[sp.p.rows] = mx;
+      w[2 * sp.p.rows] = d0;
+      w[3 * sp.p.rows] = d1;
     }
   }
 }
@@ -79,7 +70,7 @@ __global__ void __launch_bounds__(kTpThreads) token_stream_rows_count_kernel(Str
 __global__ void __launch_bounds__(kTpThreads) token_stream_rows_write_kernel(StreamRowsSpec sp) {
   __shared__ int64_t wave_before[kTpWaves], wave_total[kTpWaves], wave_bad[kTpWaves], wave_max[kTpWaves];
   const int t = threadIdx.x, lane = t & (kTpWave - 1), wv = t / kTpWave;
-  const int64_t S = sp.seq_len, rows = sp.rows;
+  const int64_t S = sp.p.seq_len, rows = sp.p.rows;
   const int64_t row0 = static_cast<int64_t>(blockIdx.x) * kTpWaves;
   const int64_t* cnt = sp.scratch;
   const bool lead = blockIdx.x == 0;  // block-uniform: the workgroup that writes the rows' limits and the counts
@@ -116,13 +107,14 @@ __global__ void __launch_bounds__(kTpThreads) token_stream_rows_write_kernel(Str
     const int64_t d0 = cnt[2 * rows + k], d1 = cnt[3 * rows + k];
     for (int64_t b = d0; b <= d1; b += kTpWave) {  // wave-uniform trip count
       int64_t q, a, lo = 0, hi = 0;
-      const bool has = tsr_doc(sp, b + lane, d1, T0, T1, &q, &a, &lo, &hi);
+      const bool has =
+          tsr_doc(sp.p.table, sp.p.n_corpus, TsOrder{sp.p.ri}, sp.p.n, b + lane, d1, T0, T1, &q, &a, &lo, &hi);
       const unsigned long long votes = __ballot(has);
       if (has) {
         const int64_t i = first + __popcll(votes & ((1ull << lane) - 1ull));
-        if (tp_seg_writes(i, 1, sp.max_segs) > 0) {
-          sp.seg_offsets[i] = tsr_seg_offset(k, rho, S, lo);
-          sp.seg_src[i] = tsr_seg_src(sp.corpus_offsets[q], a, lo);
+        if (tp_seg_writes(i, 1, sp.p.max_segs) > 0) {
+          sp.p.seg_offsets[i] = tsr_seg_offset(k, rho, S, lo);
+          sp.p.seg_src[i] = tsr_seg_src(sp.p.corpus_offsets[q], a, lo);
         }
       }
       first += __popcll(votes);
@@ -130,20 +122,20 @@ __global__ void __launch_bounds__(kTpThreads) token_stream_rows_write_kernel(Str
   }
   if (lead) {
     for (int64_t r = t; r < rows; r += kTpThreads) {
-      sp.row_start[r] = r * S;
-      sp.row_end[r] = (r + 1) * S;
+      sp.p.row_start[r] = r * S;
+      sp.p.row_end[r] = (r + 1) * S;
     }
     if (t == 0) {
       int64_t m = 0;
       for (int w = 0; w < kTpWaves; ++w) m = wave_max[w] > m ? wave_max[w] : m;
-      const bool ok = tsr_batch_ok(n_bad, n_seg, sp.max_segs);
+      const bool ok = tsr_batch_ok(n_bad, n_seg, sp.p.max_segs);
       const int64_t n_tok = tsr_batch_tokens(rows, n_bad, S);
-      if (ok) sp.seg_offsets[n_seg] = n_tok;
-      if (n_bad != 0) sp.seg_offsets[0] = 0;  // no segment was written: the entry a plan with counts[0] = -1 shows
-      sp.counts[0] = ok ? rows : -1;
-      sp.counts[1] = n_seg;
-      sp.counts[2] = n_tok;
-      sp.counts[3] = m;
+      if (ok) sp.p.seg_offsets[n_seg] = n_tok;
+      if (n_bad != 0) sp.p.seg_offsets[0] = 0;  // no segment was written: the entry a plan with counts[0] = -1 shows
+      sp.p.counts[0] = ok ? rows : -1;
+      sp.p.counts[1] = n_seg;
+      sp.p.counts[2] = n_tok;
+      sp.p.counts[3] = m;
     }
   }
 }
@@ -151,18 +143,14 @@ __global__ void __launch_bounds__(kTpThreads) token_stream_rows_write_kernel(Str
 }  // namespace
 
 int token_stream_plan_rows(const StreamRowsSpec& spec, hipStream_t st) {
-  if (spec.n < 0 || spec.n_corpus < 0 || spec.seq_len <= 0 || spec.rows < 1 || spec.stream_rows < 0) return -2;
-  if (spec.max_segs < 1 || !spec.table || !spec.seg_offsets || !spec.seg_src || !spec.scratch) return -2;
-  if (!spec.row_start || !spec.row_end || !spec.counts) return -2;
-  if (spec.n_corpus > 0 && !spec.corpus_offsets) return -2;
-  if (spec.rows > 0x7FFFFFFF / spec.seq_len) return -2;  // a batch's positions fit the int32 cu_seqlens
-  if (spec.stream_rows > INT64_MAX / spec.seq_len) return -2;
-  if (!ts_index_ok(spec.ri, spec.n) || !ts_index_ok(spec.rows_ri, spec.rows)) return -2;
+  if (!ts_plan_args_ok(spec.p) || spec.stream_rows < 0 || !spec.scratch) return -2;
+  if (spec.stream_rows > INT64_MAX / spec.p.seq_len) return -2;
+  if (!row_index_ok(spec.rows_ri, spec.p.rows)) return -2;
   if (spec.rows_ri.mode == 2) {  // a permutation of the stream's rows, asked for positions inside it
     if (spec.rows_ri.keys.n != static_cast<uint64_t>(spec.stream_rows)) return -2;
-    if (spec.rows_ri.base > spec.stream_rows - spec.rows) return -2;
+    if (spec.rows_ri.base > spec.stream_rows - spec.p.rows) return -2;
   }
-  const dim3 grid(static_cast<uint32_t>(tsr_blocks(spec.rows))), block(kTpThreads);
+  const dim3 grid(static_cast<uint32_t>(tsr_blocks(spec.p.rows))), block(kTpThreads);
   hipLaunchKernelGGL(token_stream_rows_count_kernel, grid, block, 0, st, spec);
   hipLaunchKernelGGL(token_stream_rows_write_kernel, grid, block, 0, st, spec);
   return static_cast<int>(hipGetLastError());

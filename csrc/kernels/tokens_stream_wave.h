@@ -1,11 +1,17 @@
-// Wave-level device helpers of the token stream kernels (tokens_stream.hip, tokens_stream_rows.hip) and the host
-// check of a RowIndex both launchers make. HIP only; the arithmetic they apply is tokens_stream.h.
+// Device only: the wave-level helpers of the token stream kernels (tokens_stream.hip, tokens_stream_rows.hip). The
+// arithmetic they apply is tokens_stream.h; the host replays stand in for them with serial loops.
 #pragma once
 
 #include "common.h"
 #include "tokens_stream.h"
 
 namespace ddl {
+
+// the `order` the per-lane routines of tokens_stream.h / tokens_stream_rows.h take: q = source_row(ri, position)
+struct TsOrder {
+  const RowIndex& ri;
+  __device__ __forceinline__ int64_t operator()(int64_t i) const { return source_row(ri, i); }
+};
 
 __device__ __forceinline__ int64_t ts_wave_incl_scan(int64_t v) {
   const int lane = threadIdx.x & (kTpWave - 1);
@@ -39,21 +45,6 @@ __device__ __forceinline__ int64_t ts_wave_last_le(const int64_t* table, int64_t
     ts_search_narrow(&lo, &hi, stride, k);
   }
   return lo;
-}
-
-// the checks of token_batch_descriptor on a RowIndex asked for positions [ri.base, ri.base + n)
-inline bool ts_index_ok(const RowIndex& ri, int64_t n) {
-  if (ri.mode < 0 || ri.mode > 2) return false;
-  if (ri.mode == 1 && n > 0 && !ri.idx) return false;
-  if (ri.mode != 1 && ri.base < 0) return false;
-  if (ri.mode == 2) {  // every position inside the permutation's domain, and the domain inside the network's: the
-                       // cycle walk of feistel_perm terminates only on a bijection
-    const FeistelKeys& f = ri.keys;
-    if (f.n == 0 || f.half_bits < 1 || f.half_bits > 32) return false;
-    if (f.half_bits < 32 && f.n > (uint64_t{1} << (2 * f.half_bits))) return false;
-    if (static_cast<uint64_t>(ri.base) + static_cast<uint64_t>(n) > f.n) return false;
-  }
-  return true;
 }
 
 }  // namespace ddl

@@ -1,9 +1,7 @@
 """HBM-resident token loader on the CPU (the same planning with the host ragged gather and the host collate),
 the indexed pad/pack ops on CPU tensors, and the host check of the kernel's index arithmetic."""
 
-import os
 import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -13,8 +11,8 @@ import ddl_amd
 from ddl_amd import ops
 from ddl_amd.models.tokens import SharedTokenSource
 from ddl_amd.types import DDLEnv
+from tests.host_check import run_host_check
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GB = 16
 
 
@@ -167,16 +165,4 @@ def test_output_carving_is_aligned_and_disjoint():
 def test_indexed_pad_pack_arithmetic_under_asan_ubsan(tmp_path):
     """The kernel's per-lane loops (csrc/kernels/tokens_indexed.h), replayed on the host over exact-size heap
     buffers for the corpus, the descriptor and the outputs: a plain executable, nothing preloaded."""
-    exe = str(tmp_path / "tokens_indexed_check")
-    src = os.path.join(REPO, "csrc", "kernels", "tests", "tokens_indexed_check.cpp")
-    r = subprocess.run(["g++", "-std=c++17", "-g", "-O1", "-fno-omit-frame-pointer", "-fsanitize=address,undefined",
-                        "-fno-sanitize-recover=all", src, "-o", exe], capture_output=True, text=True)
-    if r.returncode != 0:
-        if "sanitizer" in r.stderr or "cannot find" in r.stderr:
-            pytest.skip(f"sanitizer runtime unavailable: {r.stderr[-300:]}")
-        raise AssertionError(r.stderr)
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0:verify_asan_link_order=0",
-               UBSAN_OPTIONS="print_stacktrace=1")
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=300, env=env)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    assert "tokens indexed check ok" in r.stdout
+    run_host_check(tmp_path, "tokens_indexed_check", "tokens indexed check ok")

@@ -2,9 +2,7 @@
 plan, the device-planned ops on CPU tensors against the composed references, and the host check of the batch
 descriptor kernel's index arithmetic."""
 
-import os
 import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -15,8 +13,8 @@ from ddl_amd import ops
 from ddl_amd.models.tokens import SharedTokenSource
 from ddl_amd.permutation import FeistelPermutation
 from ddl_amd.types import DDLEnv
+from tests.host_check import run_host_check
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GB = 16
 COUNT_KEYS = ("n_tokens", "n_rows", "n_seg")
 
@@ -222,16 +220,4 @@ def test_batch_descriptor_arithmetic_under_asan_ubsan(tmp_path):
     """The kernel's per-lane loops (csrc/kernels/tokens_plan.h), replayed on the host over exact-size heap buffers
     for the corpus offsets, the index and the outputs, indices outside the corpus and capacities that are too
     small included: a plain executable, nothing preloaded."""
-    exe = str(tmp_path / "tokens_plan_check")
-    src = os.path.join(REPO, "csrc", "kernels", "tests", "tokens_plan_check.cpp")
-    r = subprocess.run(["g++", "-std=c++17", "-g", "-O1", "-fno-omit-frame-pointer", "-fsanitize=address,undefined",
-                        "-fno-sanitize-recover=all", src, "-o", exe], capture_output=True, text=True)
-    if r.returncode != 0:
-        if "sanitizer" in r.stderr or "cannot find" in r.stderr:
-            pytest.skip(f"sanitizer runtime unavailable: {r.stderr[-300:]}")
-        raise AssertionError(r.stderr)
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0:verify_asan_link_order=0",
-               UBSAN_OPTIONS="print_stacktrace=1")
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=300, env=env)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    assert "tokens plan check ok" in r.stdout
+    run_host_check(tmp_path, "tokens_plan_check", "tokens plan check ok")

@@ -4,7 +4,6 @@ label arithmetic (csrc/kernels/tests/token_labels_check.cpp under ASan/UBSan).""
 
 import os
 import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -14,8 +13,8 @@ import ddl_amd
 from ddl_amd import ops
 from ddl_amd.models.tokens import SharedTokenSource
 from ddl_amd.types import DDLEnv
+from tests.host_check import run_host_check
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 S = 37
 GB = 12
 
@@ -278,16 +277,4 @@ def test_checkpoint_is_independent_of_labels(corpus):
 def test_label_arithmetic_under_asan_ubsan(tmp_path):
     """ti_labels4 (csrc/kernels/tokens_indexed.h) replayed for every lane over exact-size heap buffers: a plain
     executable, nothing preloaded."""
-    exe = str(tmp_path / "token_labels_check")
-    src = os.path.join(REPO, "csrc", "kernels", "tests", "token_labels_check.cpp")
-    r = subprocess.run(["g++", "-std=c++17", "-g", "-O1", "-fno-omit-frame-pointer", "-fsanitize=address,undefined",
-                        "-fno-sanitize-recover=all", src, "-o", exe], capture_output=True, text=True)
-    if r.returncode != 0:
-        if "sanitizer" in r.stderr or "cannot find" in r.stderr:
-            pytest.skip(f"sanitizer runtime unavailable: {r.stderr[-300:]}")
-        raise AssertionError(r.stderr)
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0:verify_asan_link_order=0",
-               UBSAN_OPTIONS="print_stacktrace=1")
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=300, env=env)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    assert "token labels check ok" in r.stdout
+    run_host_check(tmp_path, "token_labels_check", "token labels check ok")

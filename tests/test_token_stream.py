@@ -2,9 +2,7 @@
 capacity of ``ops.stream_max_segments``, the overflow convention, ``ResidentTokenStreamLoader``'s CPU twin (world
 sizes, epochs, checkpoints) and the host replay of the stream kernels' index arithmetic."""
 
-import os
 import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -16,8 +14,8 @@ from ddl_amd.models.tokens import SharedTokenSource
 from ddl_amd.ops.kernels import widen_tokens
 from ddl_amd.permutation import FeistelPermutation
 from ddl_amd.types import DDLEnv
+from tests.host_check import run_host_check
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KEYS = ("input_ids", "attention_mask", "position_ids", "segment_ids", "cu_seqlens")
 
 
@@ -252,16 +250,4 @@ def test_stream_kernel_arithmetic_under_asan_ubsan(tmp_path):
     """The kernels' per-lane loops (csrc/kernels/tokens_stream.h), replayed on the host over exact-size heap
     buffers for the corpus offsets, the order, the table and the plan arrays, indices outside the corpus and
     capacities that are too small included: a plain executable, nothing preloaded."""
-    exe = str(tmp_path / "tokens_stream_check")
-    src = os.path.join(REPO, "csrc", "kernels", "tests", "tokens_stream_check.cpp")
-    r = subprocess.run(["g++", "-std=c++17", "-g", "-O1", "-fno-omit-frame-pointer", "-fsanitize=address,undefined",
-                        "-fno-sanitize-recover=all", src, "-o", exe], capture_output=True, text=True)
-    if r.returncode != 0:
-        if "sanitizer" in r.stderr or "cannot find" in r.stderr:
-            pytest.skip(f"sanitizer runtime unavailable: {r.stderr[-300:]}")
-        raise AssertionError(r.stderr)
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0:verify_asan_link_order=0",
-               UBSAN_OPTIONS="print_stacktrace=1")
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=300, env=env)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    assert "tokens stream check ok" in r.stdout
+    run_host_check(tmp_path, "tokens_stream_check", "tokens stream check ok")

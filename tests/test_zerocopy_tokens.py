@@ -1,9 +1,7 @@
 """Zero-copy token loader on the CPU (the same code path with the host ragged gather and the host collate),
 the reference of the ragged gather op, and the host check of the kernel's index arithmetic."""
 
-import os
 import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -14,8 +12,8 @@ from ddl_amd import ops
 from ddl_amd.models.tokens import SharedTokenSource, TokenBatchProducer, expected_tokens
 from ddl_amd.permutation import EpochOrder
 from ddl_amd.types import DDLEnv
+from tests.host_check import run_host_check
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GB = 16
 
 
@@ -139,16 +137,4 @@ def test_ref_gather_ragged(corpus):
 def test_ragged_index_arithmetic_under_asan_ubsan(tmp_path):
     """The kernel's tile / unit / mask arithmetic (csrc/kernels/ragged_index.h), emulated tile by tile on the
     host over exact-size heap buffers: a plain executable, nothing preloaded."""
-    exe = str(tmp_path / "ragged_index_check")
-    src = os.path.join(REPO, "csrc", "kernels", "tests", "ragged_index_check.cpp")
-    r = subprocess.run(["g++", "-std=c++17", "-g", "-O1", "-fno-omit-frame-pointer", "-fsanitize=address,undefined",
-                        "-fno-sanitize-recover=all", src, "-o", exe], capture_output=True, text=True)
-    if r.returncode != 0:
-        if "sanitizer" in r.stderr or "cannot find" in r.stderr:
-            pytest.skip(f"sanitizer runtime unavailable: {r.stderr[-300:]}")
-        raise AssertionError(r.stderr)
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0:verify_asan_link_order=0",
-               UBSAN_OPTIONS="print_stacktrace=1")
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=300, env=env)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    assert "ragged index check ok" in r.stdout
+    run_host_check(tmp_path, "ragged_index_check", "ragged index check ok")
