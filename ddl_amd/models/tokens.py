@@ -403,9 +403,9 @@ def collate_token_window(buf: torch.Tensor, layout: TokenWindowLayout, mode: str
     ones are padding (static shapes), and ``n_rows`` gives the packed count. ``labels``: the batch gains
     ``labels``, the next-token targets (``ops.ref_token_labels``), written by the same kernel."""
     from .. import ops
-    from ..ops.kernels import _label_args, _stream_handle
+    from ..ops.kernels import _stream_handle, check_ignore_index
 
-    ignore_index = _label_args(labels, ignore_index)
+    ignore_index = check_ignore_index(labels, ignore_index)
     v = _cached_views(buf.view(-1), layout, sub)
     n_tokens, n_rows, n_seg, max_seqlen, tok0 = (int(x) for x in meta[META_FIELDS * sub:META_FIELDS * (sub + 1)])
     tokens = v["tokens"][tok0:tok0 + n_tokens]

@@ -63,6 +63,15 @@ def _stream_handle(stream) -> int:
     return stream.cuda_stream
 
 
+def _stream_pair(stream, dev) -> tuple:
+    """(the raw handle the launchers take, what ``torch.cuda.stream`` takes for the allocations in front of them:
+    a raw handle as a torch stream, None for the current stream)."""
+    handle = _stream_handle(stream)
+    if isinstance(stream, int):
+        stream = torch.cuda.ExternalStream(stream, device=dev)
+    return handle, stream
+
+
 def _is_gpu(t) -> bool:
     return isinstance(t, HostRows) or (isinstance(t, torch.Tensor) and t.is_cuda)
 
@@ -76,7 +85,9 @@ def _src_addr(src) -> int:
     return src.device_ptr if isinstance(src, HostRows) else src.data_ptr()
 
 
-def _index_kw(index: torch.Tensor | None, perm: FeistelPermutation | None, base: int) -> dict:
+def row_selector(index: torch.Tensor | None = None, perm: FeistelPermutation | None = None, base: int = 0) -> dict:
+    """The ``RowIndex`` arguments of the native launchers: the rows of a device ``index``, of ``perm`` from
+    position ``base`` on, or ``base, base + 1, ...``."""
     if index is not None and perm is not None:
         raise ValueError("give either index or perm, not both")
     if index is not None:
@@ -91,6 +102,8 @@ def _index_kw(index: torch.Tensor | None, perm: FeistelPermutation | None, base:
         return dict(mode=2, idx=0, base=int(base), **perm.device_args())
     return dict(mode=0, idx=0, base=int(base), keys=[0] * 6, n_domain=1, half_bits=1)
 
+
+_index_kw = row_selector
 
 def _ref_rows(n_src: int, n_rows: int, index, perm, base) -> torch.Tensor:
     if index is not None:
@@ -295,11 +308,7 @@ def gather_ragged(src, src_offsets, idx, *, out: torch.Tensor | None = None, max
         out = torch.empty(total, dtype=flat.dtype, device=dev)
     elif not out.is_cuda or not out.is_contiguous() or out.dtype != flat.dtype or out.numel() < total:
         raise ValueError("gather_ragged: bad out tensor")
-    handle = _stream_handle(stream)
-    if isinstance(stream, int):
-        stream = torch.cuda.ExternalStream(stream, device=dev)
-    with torch.cuda.stream(stream):  # None: the current stream. The descriptor is allocated and copied on it
-        desc = torch.from_numpy(words).to(dev)  # a pageable copy: complete for the host on return
+    desc, handle, _ = _upload_words(words, dev, stream)
     base = desc.data_ptr()
     hip.gather_ragged(dst=out.data_ptr(), src=addr, src_start=base, dst_offsets=base + 8 * n,
                       tile_start=base + 8 * (2 * n + 1), n=n, n_tiles=n_tiles, elem_bytes=eb,
@@ -622,7 +631,7 @@ def ref_token_labels(input_ids: torch.Tensor, attention_mask: torch.Tensor, segm
     return lab
 
 
-def _label_args(labels: bool, ignore_index: int) -> int:
+def check_ignore_index(labels: bool, ignore_index: int) -> int:
     """The checked ``ignore_index`` (the kernels carry it as an int32)."""
     ignore_index = int(ignore_index)
     if labels and not -(1 << 31) <= ignore_index < (1 << 31):
@@ -637,7 +646,7 @@ def pad_tokens(tokens: torch.Tensor, offsets: torch.Tensor, seq_len: int, pad_id
     [B,S], ``ref_token_labels``), written by the same kernel."""
     if (tokens.dtype != torch.int32 and tokens.dtype not in _TOK16) or offsets.dtype != torch.int64:
         raise TypeError("tokens must be int32 / 16-bit and offsets int64")
-    ignore_index = _label_args(labels, ignore_index)
+    ignore_index = check_ignore_index(labels, ignore_index)
     if not tokens.is_cuda:
         r = ref_pad_tokens(tokens, offsets, seq_len, pad_id, position_dtype)
         return (*r, ref_token_labels(r[0], r[1], None, ignore_index)) if labels else r
@@ -763,7 +772,7 @@ def pack_tokens_device(tokens: torch.Tensor, offsets: torch.Tensor, seq_len: int
     ``ignore_index`` for an overflowed plan). Reference of the plan: ``pack_plan`` (host, runtime/arena.cpp).
     Graph-capturable: nothing in it synchronises with the host.
     """
-    ignore_index = _label_args(labels, ignore_index)
+    ignore_index = check_ignore_index(labels, ignore_index)
     if (tokens.dtype != torch.int32 and tokens.dtype not in _TOK16) or offsets.dtype != torch.int64:
         raise TypeError("tokens must be int32 / 16-bit and offsets int64")
     n = offsets.numel() - 1
@@ -840,7 +849,7 @@ def pack_tokens(tokens: torch.Tensor, seq_offsets, seq_len: int, pad_id: int = 0
     one host synchronisation is the read of the row count that sizes the result. Host offsets: the host
     plan (native ``pack_plan``), uploaded with the launch.
     """
-    ignore_index = _label_args(labels, ignore_index)
+    ignore_index = check_ignore_index(labels, ignore_index)
     if tokens.is_cuda and torch.is_tensor(seq_offsets) and seq_offsets.device == tokens.device:
         r = pack_tokens_device(tokens, seq_offsets.to(torch.int64), seq_len, pad_id, position_dtype, stream=stream,
                                labels=labels, ignore_index=ignore_index)
@@ -958,9 +967,7 @@ def _indexed_args(corpus, corpus_offsets, idx, position_dtype):
 
 
 def _upload_words(words: np.ndarray, dev, stream):
-    handle = _stream_handle(stream)
-    if isinstance(stream, int):
-        stream = torch.cuda.ExternalStream(stream, device=dev)
+    handle, stream = _stream_pair(stream, dev)
     with torch.cuda.stream(stream):  # None: the current stream. The descriptor is allocated and copied on it
         desc = torch.from_numpy(words).to(dev)  # a pageable copy: complete for the host on return
     return desc, handle, stream
@@ -978,7 +985,7 @@ def pad_tokens_indexed(corpus: torch.Tensor, corpus_offsets, idx, seq_len: int, 
     [B,S], ``ref_token_labels``), written by the same kernel and carved from the same buffer. A CPU corpus takes
     the reference path (``ref_gather_ragged`` + ``ref_pad_tokens`` + ``ref_token_labels``)."""
     flat, start, dofs = _indexed_args(corpus, corpus_offsets, idx, position_dtype)
-    ignore_index = _label_args(labels, ignore_index)
+    ignore_index = check_ignore_index(labels, ignore_index)
     S = int(seq_len)
     if S <= 0:
         raise ValueError("seq_len must be > 0")
@@ -1015,7 +1022,7 @@ def pack_tokens_indexed(corpus: torch.Tensor, corpus_offsets, idx, seq_len: int,
     the same buffer. A CPU corpus takes the reference path (``ref_gather_ragged`` + ``ref_pack_plan`` +
     ``ref_pack_tokens`` + ``ref_token_labels``)."""
     flat, start, dofs = _indexed_args(corpus, corpus_offsets, idx, position_dtype)
-    ignore_index = _label_args(labels, ignore_index)
+    ignore_index = check_ignore_index(labels, ignore_index)
     S = int(seq_len)
     if S <= 0:
         raise ValueError("seq_len must be > 0")
@@ -1084,7 +1091,7 @@ def launch_device_plan(plan_ptr: int, whole: torch.Tensor, *, corpus_ptr: int, c
     (``labels=True``: with ``"labels"``, written by the pack launch)."""
     h = _native.hip()
     n, S, R, M = int(n), int(seq_len), int(max_rows), int(max_segs)
-    ignore_index = _label_args(labels, ignore_index)
+    ignore_index = check_ignore_index(labels, ignore_index)
     o_src = plan_ptr
     o_off = o_src + _align16(8 * n)
     o_end = o_off + _align16(8 * (n + 1))
@@ -1213,7 +1220,7 @@ def pack_tokens_indexed_device(corpus: torch.Tensor, corpus_offsets: torch.Tenso
     plan) and both byte counts take ``labels=True``. CPU tensors take the reference path (``ref_gather_ragged`` +
     ``ref_pack_plan`` + ``ref_pack_tokens``): the same dict."""
     flat, offs, n = _device_plan_args(corpus, corpus_offsets, index, perm, base, count, seq_len, position_dtype)
-    ignore_index = _label_args(labels, ignore_index)
+    ignore_index = check_ignore_index(labels, ignore_index)
     S = int(seq_len)
     M, R = _device_plan_caps(n, flat.numel(), S, max_rows, max_segs)
     if not flat.is_cuda:
@@ -1234,9 +1241,7 @@ def pack_tokens_indexed_device(corpus: torch.Tensor, corpus_offsets: torch.Tenso
             r["labels"] = ref_token_labels(ids, mask, seg, ignore_index)
         return r
     plan_b = device_plan_bytes(n, M, R)
-    handle = _stream_handle(stream)
-    if isinstance(stream, int):
-        stream = torch.cuda.ExternalStream(stream, device=flat.device)
+    handle, stream = _stream_pair(stream, flat.device)
     with torch.cuda.stream(stream):
         buf = _token_out_buffer(out, plan_b + device_batch_bytes(R, S, M, position_dtype, labels), flat.device)
     return launch_device_plan(
@@ -1260,7 +1265,7 @@ def pad_tokens_indexed_device(corpus: torch.Tensor, corpus_offsets: torch.Tensor
     adds ``labels`` (``ref_token_labels``), as in ``pack_tokens_indexed_device``. CPU tensors take the reference
     path (``ref_gather_ragged`` + ``ref_pad_tokens``)."""
     flat, offs, n = _device_plan_args(corpus, corpus_offsets, index, perm, base, count, seq_len, position_dtype)
-    ignore_index = _label_args(labels, ignore_index)
+    ignore_index = check_ignore_index(labels, ignore_index)
     S = int(seq_len)
     if not flat.is_cuda:
         tokens, dofs = ref_gather_ragged(flat, offs, _ref_selected(offs, n, index, perm, base))
@@ -1272,9 +1277,7 @@ def pad_tokens_indexed_device(corpus: torch.Tensor, corpus_offsets: torch.Tensor
             r["labels"] = ref_token_labels(ids, mask, None, ignore_index)
         return r
     plan_b = device_plan_bytes(n)
-    handle = _stream_handle(stream)
-    if isinstance(stream, int):
-        stream = torch.cuda.ExternalStream(stream, device=flat.device)
+    handle, stream = _stream_pair(stream, flat.device)
     with torch.cuda.stream(stream):
         buf = _token_out_buffer(out, plan_b + device_batch_bytes(n, S, None, position_dtype, labels), flat.device)
     return launch_device_plan(
@@ -1454,9 +1457,7 @@ def token_stream_table(corpus_offsets: torch.Tensor, perm: FeistelPermutation | 
             return out[:n + 1]
         return t
     h = _native.hip()
-    handle = _stream_handle(stream)
-    if isinstance(stream, int):
-        stream = torch.cuda.ExternalStream(stream, device=offs.device)
+    handle, stream = _stream_pair(stream, offs.device)
     need = h.token_stream_table_scratch(n)
     with torch.cuda.stream(stream):
         if out is None:
@@ -1531,7 +1532,7 @@ def launch_stream_plan(plan_ptr: int, whole: torch.Tensor, *, corpus_ptr: int, c
     synchronises. Returns the dict of ``stream_tokens_indexed_device``."""
     h = _native.hip()
     S, R, M = int(seq_len), int(rows), int(max_segs)
-    ignore_index = _label_args(labels, ignore_index)
+    ignore_index = check_ignore_index(labels, ignore_index)
     plan = _stream_plan_layout(plan_ptr, R, M)
     o_ss, o_so, o_rs, o_re, _ = plan
     plan_kw = dict(table=table_ptr, corpus_offsets=corpus_offsets_ptr, n_corpus=n_corpus, n=n_corpus,
@@ -1554,7 +1555,7 @@ def launch_stream_plan_rows(plan_ptr: int, whole: torch.Tensor, *, corpus_ptr: i
     ``stream_rows``: the stream's full rows, ``T // seq_len``. Nothing here allocates, copies or synchronises."""
     h = _native.hip()
     S, R, M = int(seq_len), int(rows), int(max_segs)
-    ignore_index = _label_args(labels, ignore_index)
+    ignore_index = check_ignore_index(labels, ignore_index)
     plan = _stream_plan_layout(plan_ptr, R, M)
     o_ss, o_so, o_rs, o_re, o_scr = plan
     plan_kw = dict(table=table_ptr, corpus_offsets=corpus_offsets_ptr, n_corpus=n_corpus, n=n_corpus,
@@ -1591,7 +1592,7 @@ def stream_tokens_indexed_device(corpus: torch.Tensor, corpus_offsets: torch.Ten
     + 2 * rows, rows * seq_len)``. ``stream_rows``: the stream's full rows ``T // seq_len``, the domain ``row_perm``
     must have; None with ``row_perm`` on the GPU reads ``table[n]`` back, the one synchronising step here."""
     flat, offs, _ = _device_plan_args(corpus, corpus_offsets, None, None, 0, 0, seq_len, position_dtype)
-    ignore_index = _label_args(labels, ignore_index)
+    ignore_index = check_ignore_index(labels, ignore_index)
     S, R, n = int(seq_len), int(rows), offs.numel() - 1
     if R < 1 or int(row_base) < 0:
         raise ValueError("rows must be >= 1 and row_base >= 0")
@@ -1631,9 +1632,7 @@ def stream_tokens_indexed_device(corpus: torch.Tensor, corpus_offsets: torch.Ten
         _check_row_perm(row_perm, int(stream_rows), row_base, R)
         row_selector = _index_kw(None, row_perm, int(row_base))
     plan_b, batch_b = token_stream_bytes(R, S, M, position_dtype, labels, by_rows)
-    handle = _stream_handle(stream)
-    if isinstance(stream, int):
-        stream = torch.cuda.ExternalStream(stream, device=flat.device)
+    handle, stream = _stream_pair(stream, flat.device)
     with torch.cuda.stream(stream):
         buf = _token_out_buffer(out, plan_b + batch_b, flat.device)
     common = dict(corpus_ptr=flat.data_ptr(), corpus_elems=flat.numel(), tok16=flat.dtype in _TOK16,

@@ -123,6 +123,17 @@ class PrefetchedIndexedLoader:
     handoff = "device"
     block_bytes = 2 << 30  # output batches are carved from blocks of about this size (>= 1 batch, <= 64)
 
+    @staticmethod
+    def _resolve_device(env: DDLEnv, device) -> torch.device:
+        """``device``, by default the environment's (else the GPU if there is one), with a bare "cuda" resolved to
+        the current device's index."""
+        if device is None:
+            device = env.device or ("cuda" if torch.cuda.is_available() else "cpu")
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        return device
+
     def _out_batch(self, shape: tuple, dtype) -> torch.Tensor:
         """An output tensor for one batch, carved (on the current stream: the prep stream) from a block of
         batches. The caller's stream is recorded on a block once (``__iter__``), not once per batch: the caching
@@ -353,11 +364,7 @@ class ResidentGlobalLoader(PrefetchedIndexedLoader):
         self.S = -(-n // self.W)
         self.lo = self.rank * self.S
         self.hi = min(n, self.lo + self.S)
-        if device is None:
-            device = self.env.device or ("cuda" if torch.cuda.is_available() else "cpu")
-        self.device = torch.device(device)
-        if self.device.type == "cuda" and self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.device = self._resolve_device(self.env, device)
         self.out_dtype = _dtypes.to_torch_dtype(out_dtype) if out_dtype is not None else self.src_dtype
         self.normalize = normalize
         if augment is not None and (self.device.type != "cuda" or len(self.sample_shape) != 3):

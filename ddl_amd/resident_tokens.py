@@ -34,13 +34,11 @@ are therefore static and the counts of a batch are 0-d device tensors (``docs/AR
 
 from __future__ import annotations
 
-import time
-
 import numpy as np
 import torch
 
 from . import _native
-from .exceptions import DDLError
+from .corpus_replica import ResidentCorpusLoader
 from .models.tokens import SharedTokenSource, check_token_options, drop_cached_views
 from .ops.kernels import (carve_token_outputs, device_batch_bytes, device_plan_bytes, launch_device_plan,
                           pack_tokens_indexed_device, pad_tokens_indexed_device, segment_sources,
@@ -48,65 +46,9 @@ from .ops.kernels import (carve_token_outputs, device_batch_bytes, device_plan_b
 from .token_plan import HostPlannedTokenLoader
 from .types import DDLEnv
 from .utils import streams
-from .zerocopy import register_mapping, unregister_mapping
-
-# (corpus address, bytes, device index) -> [HBM tensor, users, load seconds, corpus offsets in HBM | None]
-_REPLICAS: dict[tuple, list] = {}
 
 
-def _acquire_replica(source: SharedTokenSource, nbytes: int, device: torch.device, stream, hbm_fraction: float,
-                     chunk_bytes: int) -> tuple[tuple, torch.Tensor, bool]:
-    """(key, the corpus in HBM, shared with an earlier loader). A new replica is budgeted against the free HBM
-    first; a failure leaves nothing allocated or registered."""
-    key = (int(source.tokens.address), int(nbytes), device.index)
-    rep = _REPLICAS.get(key)
-    if rep is not None:
-        rep[1] += 1
-        return key, rep[0], True
-    free, _ = torch.cuda.mem_get_info(device)
-    if nbytes > hbm_fraction * free:
-        raise DDLError(f"the corpus ({nbytes} bytes) exceeds hbm_fraction={hbm_fraction} of the free HBM "
-                       f"({free} bytes free, {int(hbm_fraction * free)} allowed); a corpus is not sharded across "
-                       "ranks: use ZeroCopyTokenLoader, which reads it from host memory")
-    t0 = time.perf_counter()
-    hip = _native.hip()
-    hbm = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
-    if nbytes:
-        torch.cuda.synchronize(device)  # the block may be a cached one: nothing of its past is still running
-        base, _ = register_mapping(source.tokens.address, nbytes, shared=True)  # pinned: the copies are SDMA
-        try:
-            step = max(1, int(chunk_bytes))
-            for o in range(0, nbytes, step):
-                hip.memcpy_h2d(hbm.data_ptr() + o, source.tokens.address + o, min(step, nbytes - o),
-                               stream.cuda_stream)
-            stream.synchronize()
-        finally:
-            unregister_mapping(base, device, shared=True)
-    _REPLICAS[key] = [hbm, 1, time.perf_counter() - t0, None]
-    return key, hbm, False
-
-
-def _replica_offsets(key: tuple, offsets: torch.Tensor, device: torch.device, stream) -> torch.Tensor:
-    """The corpus offsets (int64 [n + 1]) in HBM, for plans built on the device: uploaded once per replica by the
-    first loader that asks, shared and freed with it."""
-    rep = _REPLICAS[key]
-    if rep[3] is None:
-        with streams.on_stream(stream):
-            rep[3] = offsets.to(device)
-        stream.synchronize()  # bring-up: later loaders over this replica use it from their own streams
-    return rep[3]
-
-
-def _release_replica(key: tuple) -> None:
-    rep = _REPLICAS.get(key)
-    if rep is None:
-        return
-    rep[1] -= 1
-    if rep[1] <= 0:
-        del _REPLICAS[key]  # the last reference: the allocation goes back to the allocator
-
-
-class ResidentTokenLoader(HostPlannedTokenLoader):
+class ResidentTokenLoader(ResidentCorpusLoader, HostPlannedTokenLoader):
     def __init__(self, source: SharedTokenSource, global_batch: int, seq_len: int = 4096, mode: str = "pad",
                  env: DDLEnv | None = None, *, seed: int = 0, pack_order: str = "in_order",
                  token_rows: str | None = None, pad_id: int = 0, depth: int = 2,
@@ -135,17 +77,7 @@ class ResidentTokenLoader(HostPlannedTokenLoader):
             raise ValueError(f"{self.LB} sequences of up to {source.max_len} tokens in one batch can overflow int32 "
                              "cu_seqlens")
         self.n_elems = self.nbytes // source.token_bytes
-        self._replica_key = None
-        self.replica_shared = False
-        self.load_s = 0.0
-        self.assemble_s = 0.0  # wall time spent in _assemble (host_us_per_step of the benchmark)
-        self.profile_every = 0  # > 0: device events around the launch of every profile_every-th step
-        self._kernel_evs: list = []
-        gpu = self.prep_stream is not None
-        if gpu:
-            self._replica_key, self._hbm, self.replica_shared = _acquire_replica(
-                source, self.nbytes, self.device, self.prep_stream, float(hbm_fraction), chunk_bytes)
-            self.load_s = _REPLICAS[self._replica_key][2]
+        gpu = self._attach_replica(hbm_fraction, chunk_bytes)
         if plan == "device":
             self._init_device_plan(gpu)
             return
@@ -156,14 +88,13 @@ class ResidentTokenLoader(HostPlannedTokenLoader):
         return "seg_src", np.int64, self.layout.max_segments  # the corpus element of each segment's first token
 
     def _init_device_plan(self, gpu: bool) -> None:
-        """plan="device": the corpus offsets in HBM, a ring of plan windows (the arrays between the launches;
-        nothing a caller holds) and the per-epoch selectors. The CPU twin needs none of it."""
+        """plan="device": the corpus offsets in HBM and a ring of plan windows (the arrays between the launches;
+        nothing a caller holds). The CPU twin needs neither."""
         lay, pack = self.layout, self.mode == "pack"
-        self._selectors: dict = {}
         self._max_seqlen = min(self.seq_len, self.source.max_len)
         if not gpu:
             return
-        self._offs_dev = _replica_offsets(self._replica_key, self._offs_t, self.device, self.prep_stream)
+        self._replica.offsets(self._offs_t, self.prep_stream)
         segs = lay.max_segments if pack else None
         self._plan_bytes = device_plan_bytes(self.LB, segs, lay.max_segments if pack else 0)
         self._batch_bytes = device_batch_bytes(lay.max_segments if pack else self.LB, self.seq_len, segs,
@@ -171,27 +102,15 @@ class ResidentTokenLoader(HostPlannedTokenLoader):
         self._windows = [torch.empty(self._plan_bytes, dtype=torch.uint8, device=self.device)
                          for _ in range(self.depth + 1)]
 
-    def _selector(self, epoch: int) -> dict:
-        """The ``RowIndex`` arguments of epoch ``epoch``'s order (its Feistel round keys), minus the base."""
-        sel = self._selectors.get(epoch)
-        if sel is None:
-            if len(self._selectors) > 8:
-                self._selectors.clear()
-            perm = self.order.perm(epoch)
-            sel = dict(mode=2, idx=0, **perm.device_args()) if self.order.shuffle else dict(
-                mode=0, idx=0, keys=[0] * 6, n_domain=1, half_bits=1)
-            self._selectors[epoch] = sel
-        return sel
+    def _perm(self, epoch: int):
+        return self.order.perm(epoch) if self.order.shuffle else None
 
-    def _assemble_device_plan(self, t: int):
-        t_host = time.perf_counter()
+    def _step_device_plan(self, t: int):
         e, g = divmod(t, self.order.batches_per_epoch)
         base = g * self.GB + self.rank * self.LB
         lay, S, LB, pack = self.layout, self.seq_len, self.LB, self.mode == "pack"
-        st = self.prep_stream
-        if st is None:  # the CPU twin: the op's reference path
-            perm = self.order.perm(e) if self.order.shuffle else None
-            kw = dict(perm=perm, base=base, count=LB, seq_len=S, pad_id=self.pad_id, labels=self.labels,
+        if self.prep_stream is None:  # the CPU twin: the op's reference path
+            kw = dict(perm=self._perm(e), base=base, count=LB, seq_len=S, pad_id=self.pad_id, labels=self.labels,
                       ignore_index=self.ignore_index)
             if pack:
                 r = pack_tokens_indexed_device(self._toks, self._offs_t, max_rows=lay.max_segments,
@@ -200,50 +119,28 @@ class ResidentTokenLoader(HostPlannedTokenLoader):
                 r = pad_tokens_indexed_device(self._toks, self._offs_t, **kw)
             ev = None
         else:
-            timed = self.profile_every > 0 and t % self.profile_every == 0
-            win = self._windows[t % len(self._windows)]
-            with streams.on_stream(st):
-                # one allocation for everything the caller may hold (outputs, cu_seqlens, counts): a held batch
-                # survives the ring of plan windows
-                whole = torch.empty(self._batch_bytes, dtype=torch.uint8, device=self.device)
-                if timed:
-                    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    ev0.record(st)
-                r = launch_device_plan(
-                    win.data_ptr(), whole, corpus_ptr=self._hbm.data_ptr(), corpus_elems=self.n_elems,
-                    tok16=self.source.token_bytes == 2, corpus_offsets_ptr=self._offs_dev.data_ptr(),
-                    n_corpus=self.source.n, selector=dict(self._selector(e), base=base), n=LB, seq_len=S,
-                    pad_id=self.pad_id, pack=pack, max_segs=lay.max_segments if pack else 0,
-                    max_rows=lay.max_segments if pack else 0, stream=st.cuda_stream, labels=self.labels,
-                    ignore_index=self.ignore_index)
-                if timed:
-                    ev1.record(st)
-                    self._kernel_evs.append((ev0, ev1))
-                ev = torch.cuda.Event()
-                ev.record(st)
+            rep = self._replica
+            r, ev = self._launch(t, self._batch_bytes, lambda win, whole: launch_device_plan(
+                win.data_ptr(), whole, corpus_ptr=rep.hbm.data_ptr(), corpus_elems=self.n_elems,
+                tok16=self.source.token_bytes == 2, corpus_offsets_ptr=rep.offsets_dev.data_ptr(),
+                n_corpus=self.source.n, selector=dict(self._selector(e), base=base), n=LB, seq_len=S,
+                pad_id=self.pad_id, pack=pack, max_segs=lay.max_segments if pack else 0,
+                max_rows=lay.max_segments if pack else 0, stream=self.prep_stream.cuda_stream, labels=self.labels,
+                ignore_index=self.ignore_index))
         counts = r.pop("counts")
         r["n_tokens"] = counts[2]
         if pack:
             r["max_seqlen"] = self._max_seqlen  # a static upper bound (varlen attention accepts one)
             r["n_rows"], r["n_seg"] = counts[0], counts[1]
-        self.assemble_s += time.perf_counter() - t_host
         return r, ev
 
-    @property
-    def replica_ptr(self) -> int | None:
-        """Device address of the corpus replica (None on the CPU, and after ``close``)."""
-        return self._hbm.data_ptr() if self._replica_key is not None else None
-
-    def _assemble(self, t: int):
+    def _step(self, t: int):
         if self.plan == "device":
-            return self._assemble_device_plan(t)
-        t_host = time.perf_counter()
+            return self._step_device_plan(t)
         k, v, idx, meta = self._plan(t)
         n_tokens, n_rows, n_seg, max_seg, _ = meta
         if self.prep_stream is None:
-            batch = self._cpu_batch(t, v, idx, meta)
-            self.assemble_s += time.perf_counter() - t_host
-            return batch, None
+            return self._cpu_batch(t, v, idx, meta), None
         if n_tokens > 0x7FFFFFFF:
             raise ValueError(f"{n_tokens} tokens in one batch overflow int32 cu_seqlens")
         lay, S, LB = self.layout, self.seq_len, self.LB
@@ -253,6 +150,8 @@ class ResidentTokenLoader(HostPlannedTokenLoader):
         hip, st = _native.hip(), self.prep_stream
         fill = lay.max_segments if (pack and fixed) else 0
         R = max(n_rows, fill) if pack else LB
+        # the frame of ResidentCorpusLoader._launch, written out: this step has an H2D copy and the carving in
+        # front of the timed launch, and the calls _launch makes cost it 1.5-3 us of its 37 (pad mode)
         timed = self.profile_every > 0 and t % self.profile_every == 0
         win = self._windows[t % len(self._windows)]
         with streams.on_stream(st):
@@ -269,7 +168,7 @@ class ResidentTokenLoader(HostPlannedTokenLoader):
                 ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 ev0.record(st)
             hip.pad_pack_tokens_indexed(
-                corpus=self._hbm.data_ptr(), corpus_elems=self.n_elems, src_start=w, seg_src=w + 8 * LB,
+                corpus=self._replica.hbm.data_ptr(), corpus_elems=self.n_elems, src_start=w, seg_src=w + 8 * LB,
                 offsets=h + self._reg["offsets"][0], row_start=h + self._reg["row_start"][0],
                 row_end=h + self._reg["row_end"][0], seg_offsets=h + self._reg["seg_offsets"][0], n_seg=n_seg,
                 out_tokens=ids.data_ptr(), attn_mask=mask.data_ptr(), position_ids=pos.data_ptr(), pos_is_i64=True,
@@ -291,20 +190,7 @@ class ResidentTokenLoader(HostPlannedTokenLoader):
             batch = {"input_ids": ids, "attention_mask": mask, "position_ids": pos, "n_tokens": n_tokens}
         if lab:
             batch["labels"] = lab[0]
-        self.assemble_s += time.perf_counter() - t_host
         return batch, ev
-
-    def timing(self) -> dict:
-        """``host_us_per_step``: mean wall time of ``_assemble`` (planning, the H2D and the launch, on the host);
-        ``kernel_us``: mean device time of the sampled launches (``profile_every``), None without samples.
-        Synchronises the prep stream."""
-        steps = max(1, self.batches + len(self._queue))  # batches assembled so far
-        out = {"host_us_per_step": 1e6 * self.assemble_s / steps, "kernel_us": None,
-               "kernel_samples": len(self._kernel_evs)}
-        if self._kernel_evs:
-            self.prep_stream.synchronize()
-            out["kernel_us"] = 1e3 * sum(a.elapsed_time(b) for a, b in self._kernel_evs) / len(self._kernel_evs)
-        return out
 
     def stats(self) -> dict:
         out = {"batches": self.batches, "source_bytes": self.nbytes, "load_s": self.load_s,
@@ -323,8 +209,4 @@ class ResidentTokenLoader(HostPlannedTokenLoader):
             if self.prep_stream is None and self.plan == "host":
                 drop_cached_views(w.data_ptr() + self._desc_bytes for w in self._windows)
             self._windows = []
-        if self._replica_key is not None:
-            key, self._replica_key = self._replica_key, None
-            self._hbm = None
-            self._offs_dev = None
-            _release_replica(key)
+        self._release_replica()

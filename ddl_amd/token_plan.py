@@ -16,6 +16,7 @@ import torch
 from . import _native
 from .models.tokens import (META_FIELDS, SharedTokenSource, TokenWindowLayout, collate_token_window,
                             ffd_if_it_wins)
+from .ops.kernels import check_ignore_index
 from .permutation import EpochOrder
 from .resident import PrefetchedIndexedLoader
 from .types import DDLEnv
@@ -31,9 +32,7 @@ class HostPlannedTokenLoader(PrefetchedIndexedLoader):
         in front of its own rules. ``labels``: every batch gains ``"labels"``, the next-token targets
         (``ops.ref_token_labels``) with ``ignore_index`` where there is none, written by the kernel that writes the
         batch; nothing else of the loader (order, checkpoint, stats) depends on it."""
-        self.labels, self.ignore_index = bool(labels), int(ignore_index)
-        if self.labels and not -(1 << 31) <= self.ignore_index < (1 << 31):
-            raise ValueError(f"ignore_index={ignore_index} does not fit int32")
+        self.labels, self.ignore_index = bool(labels), check_ignore_index(labels, ignore_index)
         self.handoff = handoff
         self.env = env or DDLEnv()
         self.W, self.rank = self.env.world_size, self.env.rank
@@ -42,11 +41,7 @@ class HostPlannedTokenLoader(PrefetchedIndexedLoader):
         self.order = EpochOrder(source.n, global_batch, seed)
         self.GB, self.LB = int(global_batch), self.order.local_batch(self.W)
         self.out_dtype = torch.int32  # input_ids (the checkpoint's dtype field)
-        if device is None:
-            device = self.env.device or ("cuda" if torch.cuda.is_available() else "cpu")
-        self.device = torch.device(device)
-        if self.device.type == "cuda" and self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.device = self._resolve_device(self.env, device)
         self._init_cursor(seed, depth, n_epochs, resume_state)
 
         lay = self.layout = TokenWindowLayout(self.LB, self.seq_len, source.max_len, 1, source.token_bytes)

@@ -13,8 +13,9 @@ every world size (rank ``r`` of ``W`` takes rows ``[g * GB + r * LB, g * GB + (r
 ``g``). ``rows_per_epoch = T // S`` and ``batches_per_epoch = rows_per_epoch // global_batch``; the tail is
 dropped, a different one each epoch under ``shuffle``.
 
-Nothing is planned on the host. The corpus replica and its offsets are ``ResidentTokenLoader``'s (shared with
-any over the same corpus). Once per epoch the ``token_stream_table`` kernels scan the documents' lengths in the
+Nothing is planned on the host. The corpus replica and its offsets are a ``CorpusReplica`` (shared with
+any ``ResidentTokenLoader`` over the same corpus). Once per epoch the ``token_stream_table`` kernels scan the
+documents' lengths in the
 epoch's order (the Feistel permutation inline) into ``table [n + 1]``; per step ``token_stream_plan`` finds the
 window's documents in it and writes the pack plan -- a segment is a maximal run of one document inside one row,
 ``position_ids`` restart in every segment -- which the unchanged ``pad_pack_tokens_indexed`` renders: two
@@ -34,19 +35,17 @@ epoch on the host.
 
 from __future__ import annotations
 
-import time
-
 import numpy as np
 import torch
 
 from . import _native
+from .corpus_replica import ResidentCorpusLoader
 from .exceptions import DDLError
 from .models.tokens import SharedTokenSource
-from .ops.kernels import (launch_stream_plan, launch_stream_plan_rows, ref_stream_tokens, stream_max_segments,
-                          token_stream_bytes)
+from .ops.kernels import (check_ignore_index, launch_stream_plan, launch_stream_plan_rows, ref_stream_tokens,
+                          stream_max_segments, token_stream_bytes)
 from .permutation import FeistelPermutation, row_seed_for
 from .resident import STATE_VERSION, PrefetchedIndexedLoader
-from .resident_tokens import _REPLICAS, _acquire_replica, _release_replica, _replica_offsets
 from .types import DDLEnv
 from .utils import streams
 
@@ -59,7 +58,7 @@ class _RowOrder:
         self.batches_per_epoch = rows_per_epoch // global_batch
 
 
-class ResidentTokenStreamLoader(PrefetchedIndexedLoader):
+class ResidentTokenStreamLoader(ResidentCorpusLoader, PrefetchedIndexedLoader):
     def __init__(self, source: SharedTokenSource, global_batch: int, seq_len: int = 4096, env: DDLEnv | None = None,
                  *, seed: int = 0, shuffle: bool = True, pad_id: int = 0, depth: int = 2,
                  device: str | torch.device | None = None, n_epochs: int | None = None,
@@ -73,9 +72,7 @@ class ResidentTokenStreamLoader(PrefetchedIndexedLoader):
         unshuffled stream."""
         if handoff not in ("device", "host"):
             raise ValueError("handoff must be 'device' or 'host'")
-        self.labels, self.ignore_index = bool(labels), int(ignore_index)
-        if self.labels and not -(1 << 31) <= self.ignore_index < (1 << 31):
-            raise ValueError(f"ignore_index={ignore_index} does not fit int32")
+        self.labels, self.ignore_index = bool(labels), check_ignore_index(labels, ignore_index)
         self.handoff = handoff
         self.env = env or DDLEnv()
         self.W, self.rank = self.env.world_size, self.env.rank
@@ -105,30 +102,15 @@ class ResidentTokenStreamLoader(PrefetchedIndexedLoader):
             raise ValueError("max_segments must be >= 1")
         self._max_seqlen = min(self.seq_len, int(source.max_len))
         self.out_dtype = torch.int32
-        if device is None:
-            device = self.env.device or ("cuda" if torch.cuda.is_available() else "cpu")
-        self.device = torch.device(device)
-        if self.device.type == "cuda" and self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.device = self._resolve_device(self.env, device)
         self._init_cursor(seed, depth, n_epochs, resume_state)
         self.nbytes = int(offs[-1]) * source.token_bytes if source.n else 0
         self.n_elems = self.nbytes // source.token_bytes
         self.prep_stream = streams.batch_stream(self.device) if self.device.type == "cuda" else None
-        self._replica_key = None
-        self.replica_shared = False
-        self.load_s = 0.0
-        self.assemble_s = 0.0  # wall time spent in _assemble (host_us_per_step of the benchmark)
-        self.profile_every = 0  # > 0: device events around the launches of every profile_every-th step
-        self._kernel_evs: list = []
         self.tables_built = 0
-        self._selectors: dict = {}
-        self._row_selectors: dict = {}
         self._windows: list = []
-        if self.prep_stream is None:
+        if not self._attach_replica(hbm_fraction, chunk_bytes):
             return
-        self._replica_key, self._hbm, self.replica_shared = _acquire_replica(
-            source, self.nbytes, self.device, self.prep_stream, float(hbm_fraction), chunk_bytes)
-        self.load_s = _REPLICAS[self._replica_key][2]
         try:
             n = self.n_documents
             scratch = _native.hip().token_stream_table_scratch(n)
@@ -137,7 +119,7 @@ class ResidentTokenStreamLoader(PrefetchedIndexedLoader):
             if table_bytes > float(hbm_fraction) * free:
                 raise DDLError(f"the two epoch tables ({table_bytes} bytes) exceed hbm_fraction={hbm_fraction} of "
                                f"the free HBM ({free} bytes free)")
-            self._offs_dev = _replica_offsets(self._replica_key, self._offs_t, self.device, self.prep_stream)
+            self._replica.offsets(self._offs_t, self.prep_stream)
             with streams.on_stream(self.prep_stream):
                 # two tables: prefetch crosses the epoch boundary (epoch e lives in slot e % 2)
                 self._tables = [torch.empty(n + 1, dtype=torch.int64, device=self.device) for _ in range(2)]
@@ -156,46 +138,23 @@ class ResidentTokenStreamLoader(PrefetchedIndexedLoader):
     def _perm(self, epoch: int) -> FeistelPermutation | None:
         return FeistelPermutation(self.n_documents, self.seed, epoch) if self.order.shuffle else None
 
-    def _selector(self, epoch: int) -> dict:
-        """The ``RowIndex`` arguments of epoch ``epoch``'s document order (its Feistel round keys), base 0."""
-        sel = self._selectors.get(epoch)
-        if sel is None:
-            if len(self._selectors) > 8:
-                self._selectors.clear()
-            perm = self._perm(epoch)
-            sel = dict(mode=2, idx=0, base=0, **perm.device_args()) if perm is not None else dict(
-                mode=0, idx=0, base=0, keys=[0] * 6, n_domain=1, half_bits=1)
-            self._selectors[epoch] = sel
-        return sel
-
     def _row_perm(self, epoch: int) -> FeistelPermutation | None:
         return FeistelPermutation(self.order.n_samples, self.row_seed, epoch) if self.shuffle_rows else None
 
-    def _row_selector(self, epoch: int) -> dict:
-        """The ``RowIndex`` arguments of epoch ``epoch``'s row permutation; a step sets its own ``base``."""
-        sel = self._row_selectors.get(epoch)
-        if sel is None:
-            if len(self._row_selectors) > 8:
-                self._row_selectors.clear()
-            sel = dict(mode=2, idx=0, base=0, **self._row_perm(epoch).device_args())
-            self._row_selectors[epoch] = sel
-        return sel
-
     def _table(self, epoch: int, sel: dict) -> torch.Tensor:
-        """Epoch ``epoch``'s table, built on the prep stream (the current one) the first time a step of the epoch
+        """Epoch ``epoch``'s table, built on the prep stream the first time a step of the epoch
         is assembled. The slot's earlier epoch is two behind: every step that reads it was enqueued before."""
         k = epoch % 2
         if self._table_epoch[k] != epoch:
             _native.hip().token_stream_table(
-                corpus_offsets=self._offs_dev.data_ptr(), n_corpus=self.n_documents, n=self.n_documents,
+                corpus_offsets=self._replica.offsets_dev.data_ptr(), n_corpus=self.n_documents, n=self.n_documents,
                 table=self._tables[k].data_ptr(), tile_sums=self._scratch.data_ptr(),
                 stream=self.prep_stream.cuda_stream, **sel)
             self._table_epoch[k] = epoch
             self.tables_built += 1
         return self._tables[k]
 
-    def _assemble(self, t: int):
-        t_host = time.perf_counter()
+    def _step(self, t: int):
         e, g = divmod(t, self.order.batches_per_epoch)
         row_base = g * self.GB + self.rank * self.LB
         st = self.prep_stream
@@ -205,37 +164,27 @@ class ResidentTokenStreamLoader(PrefetchedIndexedLoader):
                                   labels=self.labels, ignore_index=self.ignore_index, row_perm=self._row_perm(e))
             ev = None
         else:
-            timed = self.profile_every > 0 and t % self.profile_every == 0
-            win = self._windows[t % len(self._windows)]
             sel = self._selector(e)
-            with streams.on_stream(st):
-                table = self._table(e, sel)
-                # one allocation for everything the caller may hold (outputs, cu_seqlens, counts): a held batch
-                # survives the ring of plan windows
-                whole = torch.empty(self._batch_bytes, dtype=torch.uint8, device=self.device)
-                if timed:
-                    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    ev0.record(st)
+            table = self._table(e, sel)
+
+            def issue(win, whole):
+                rep = self._replica
                 common = dict(
-                    corpus_ptr=self._hbm.data_ptr(), corpus_elems=self.n_elems,
-                    tok16=self.source.token_bytes == 2, corpus_offsets_ptr=self._offs_dev.data_ptr(),
+                    corpus_ptr=rep.hbm.data_ptr(), corpus_elems=self.n_elems,
+                    tok16=self.source.token_bytes == 2, corpus_offsets_ptr=rep.offsets_dev.data_ptr(),
                     n_corpus=self.n_documents, table_ptr=table.data_ptr(), selector=sel,
                     rows=self.LB, seq_len=self.seq_len, pad_id=self.pad_id, max_segs=self.max_segments,
                     stream=st.cuda_stream, labels=self.labels, ignore_index=self.ignore_index)
                 if self.shuffle_rows:
-                    r = launch_stream_plan_rows(win.data_ptr(), whole, stream_rows=self.order.n_samples,
-                                                row_selector=dict(self._row_selector(e), base=row_base), **common)
-                else:
-                    r = launch_stream_plan(win.data_ptr(), whole, row_base=row_base, **common)
-                if timed:
-                    ev1.record(st)
-                    self._kernel_evs.append((ev0, ev1))
-                ev = torch.cuda.Event()
-                ev.record(st)
+                    return launch_stream_plan_rows(
+                        win.data_ptr(), whole, stream_rows=self.order.n_samples,
+                        row_selector=dict(self._selector(e, self._row_perm), base=row_base), **common)
+                return launch_stream_plan(win.data_ptr(), whole, row_base=row_base, **common)
+
+            r, ev = self._launch(t, self._batch_bytes, issue)
         counts = r.pop("counts")
         r["max_seqlen"] = self._max_seqlen  # a static upper bound (varlen attention accepts one)
         r["n_tokens"], r["n_rows"], r["n_seg"] = counts[2], counts[0], counts[1]
-        self.assemble_s += time.perf_counter() - t_host
         return r, ev
 
     # ----------------------------------------------------------- checkpoint
@@ -277,23 +226,6 @@ class ResidentTokenStreamLoader(PrefetchedIndexedLoader):
             self.epoch, self.cursor = self.epoch + 1, 0
 
     # ---------------------------------------------------------------- misc
-    @property
-    def replica_ptr(self) -> int | None:
-        """Device address of the corpus replica (None on the CPU, and after ``close``)."""
-        return self._hbm.data_ptr() if self._replica_key is not None else None
-
-    def timing(self) -> dict:
-        """``host_us_per_step``: mean wall time of ``_assemble`` (the launches, on the host); ``kernel_us``: mean
-        device time of the sampled steps' launches (``profile_every``; an epoch's first step includes its table),
-        None without samples. Synchronises the prep stream."""
-        steps = max(1, self.batches + len(self._queue))
-        out = {"host_us_per_step": 1e6 * self.assemble_s / steps, "kernel_us": None,
-               "kernel_samples": len(self._kernel_evs)}
-        if self._kernel_evs:
-            self.prep_stream.synchronize()
-            out["kernel_us"] = 1e3 * sum(a.elapsed_time(b) for a, b in self._kernel_evs) / len(self._kernel_evs)
-        return out
-
     def stats(self) -> dict:
         return {"batches": self.batches, "source_bytes": self.nbytes, "load_s": self.load_s,
                 "load_gbps": self.nbytes / self.load_s / 1e9 if self.load_s > 0 else 0.0, "handoff": self.handoff,
@@ -309,11 +241,7 @@ class ResidentTokenStreamLoader(PrefetchedIndexedLoader):
         self._kernel_evs = []
         self._windows = []
         self._tables = self._scratch = None
-        if getattr(self, "_replica_key", None) is not None:
-            key, self._replica_key = self._replica_key, None
-            self._hbm = None
-            self._offs_dev = None
-            _release_replica(key)
+        self._release_replica()
 
     def __del__(self):  # pragma: no cover - best effort
         try:

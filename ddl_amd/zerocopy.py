@@ -137,11 +137,7 @@ class ZeroCopyLoader(PrefetchedIndexedLoader):
             out_bytes = torch.empty((), dtype=self.out_dtype).element_size()
             max_blocks = 32 if out_bytes <= src_bytes else 0
         self.max_blocks = int(max_blocks)
-        if device is None:
-            device = self.env.device or ("cuda" if torch.cuda.is_available() else "cpu")
-        self.device = torch.device(device)
-        if self.device.type == "cuda" and self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.device = self._resolve_device(self.env, device)
         self._init_cursor(seed, depth, n_epochs, resume_state)
         self.cpu = _cpu_view(source, n, self.sample_shape, self.src_dtype)
         self._source = source  # keep the mapping alive

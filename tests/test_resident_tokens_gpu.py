@@ -6,7 +6,7 @@ import pytest
 import torch
 
 import ddl_amd
-from ddl_amd import _native, ops, resident_tokens
+from ddl_amd import _native, corpus_replica, ops
 from ddl_amd.exceptions import DDLError
 from ddl_amd.models.tokens import SharedTokenSource
 from ddl_amd.types import DDLEnv
@@ -253,8 +253,8 @@ def test_two_loaders_share_one_replica():
         b = ddl_amd.ResidentTokenLoader(corpus, GB, 100, "pack", seed=4, n_epochs=1)
         assert a.replica_ptr == b.replica_ptr and a.replica_ptr is not None
         assert a.stats()["replica_shared"] is False and b.stats()["replica_shared"] is True
-        key = a._replica_key
-        assert resident_tokens._REPLICAS[key][1] == 2
+        key = a._replica.key
+        assert b._replica is a._replica and corpus_replica.REPLICAS[key].users == 2
         assert torch.cuda.memory_allocated() >= before + a.nbytes
         ita, itb = iter(a), iter(b)
         for g in range(3):
@@ -262,12 +262,12 @@ def test_two_loaders_share_one_replica():
             _same(next(itb), ref[g])
         del ita
         a.close()
-        assert a.replica_ptr is None and resident_tokens._REPLICAS[key][1] == 1
+        assert a.replica_ptr is None and corpus_replica.REPLICAS[key].users == 1
         for g in range(3, 12):
             _same(next(itb), ref[g])
         del itb
         b.close()
-        assert key not in resident_tokens._REPLICAS
+        assert key not in corpus_replica.REPLICAS
         assert torch.cuda.memory_allocated() <= before  # the replica (and every window) went back to the allocator
     finally:
         corpus.close()
@@ -282,12 +282,12 @@ def test_over_budget_corpus_is_refused_and_leaves_nothing_behind():
         with pytest.raises(DDLError) as err:
             ddl_amd.ResidentTokenLoader(corpus, GB, 100, "pack", seed=4, hbm_fraction=0.0)
         assert str(nbytes) in str(err.value) and "ZeroCopyTokenLoader" in str(err.value)
-        assert not resident_tokens._REPLICAS and not zerocopy._SHARED_REGS
+        assert not corpus_replica.REPLICAS and not zerocopy._SHARED_REGS
         ref = _twin(corpus, 1, 100, "pack")
         dl = ddl_amd.ResidentTokenLoader(corpus, GB, 100, "pack", seed=4, n_epochs=1)  # a normal construction works
         for a, b in zip(list(dl), ref):
             _same(a, b)
         dl.close()
-        assert not resident_tokens._REPLICAS and not zerocopy._SHARED_REGS
+        assert not corpus_replica.REPLICAS and not zerocopy._SHARED_REGS
     finally:
         corpus.close()
