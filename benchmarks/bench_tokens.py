@@ -62,6 +62,9 @@ def main(argv=None):
     ap.add_argument("--shuffle-rows", action="store_true",
                     help="with --stream: the epoch's rows in a shuffled order (shuffle_rows=True: the per-row plan "
                          "kernels in place of the contiguous plan)")
+    ap.add_argument("--mix", default=None, metavar="R0,R1,...",
+                    help="with --stream: repeats of equal parts of the corpus, e.g. 2,1,0.5 (TokenMix: the epoch's "
+                         "document order is written by token_mix_order and read as an explicit index)")
     ap.add_argument("--max-blocks", type=int, default=None,
                     help="zerocopy: grid cap of the gather kernel (0 = uncapped; default: the loader's)")
     ap.add_argument("--labels", action="store_true",
@@ -78,6 +81,8 @@ def main(argv=None):
         ap.error("--stream needs --path resident, and is neither --plan device nor --mode pad")
     if a.shuffle_rows and not a.stream:
         ap.error("--shuffle-rows needs --stream")
+    if a.mix and not a.stream:
+        ap.error("--mix needs --stream")
     if a.plan == "device" and a.mode == "pack":
         if a.pack_order != "in_order":
             ap.error("--plan device builds the in-order plan: pass --pack-order in_order")
@@ -125,8 +130,12 @@ def main(argv=None):
             n_epochs = (a.warmup + a.steps + a.idle_steps + a.warmup // 2) // (a.n_seqs // gb) + 2
             pack_order = a.pack_order if a.mode == "pack" else "in_order"
             if a.stream:
+                mix = None
+                if a.mix:  # equal parts of the corpus, by document index
+                    repeat = [float(r) for r in a.mix.split(",")]
+                    mix = ddl_amd.TokenMix([round(p * a.n_seqs / len(repeat)) for p in range(len(repeat) + 1)], repeat)
                 dl = ddl_amd.ResidentTokenStreamLoader(source, gb, a.seq_len, env, labels=a.labels,
-                                                       shuffle_rows=a.shuffle_rows)
+                                                       shuffle_rows=a.shuffle_rows, mix=mix)
                 dl.profile_every = a.kernel_sample
             elif resident:
                 dl = ddl_amd.ResidentTokenLoader(source, gb, a.seq_len, a.mode, env, pack_order=pack_order,
@@ -246,7 +255,12 @@ def main(argv=None):
                                 "replica_shared": st["replica_shared"], "plan": "stream" if a.stream else a.plan}
                     if a.stream:
                         per_path.update(format="stream", max_segments=st["max_segments"],
-                                        tables_built=st["tables_built"], shuffle_rows=st["shuffle_rows"])
+                                        tables_built=st["tables_built"], shuffle_rows=st["shuffle_rows"],
+                                        mix=a.mix, mix_parts=st["mix_parts"], mix_documents=st["mix_documents"],
+                                        orders_built=st["orders_built"],
+                                        epoch_prep_us=None if timing["epoch_prep_us"] is None
+                                        else round(timing["epoch_prep_us"], 1),
+                                        epoch_prep_samples=timing["epoch_prep_samples"])
                 elif zc:
                     per_path = {"path": "zerocopy", "max_blocks": st["max_blocks"], "host_waits": st["host_waits"],
                                 "prefault_s": round(st["prefault_s"], 3)}

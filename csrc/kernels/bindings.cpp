@@ -871,6 +871,40 @@ PYBIND11_MODULE(_ddl_hip, m) {
       py::arg("rows_n_domain"), py::arg("rows_half_bits"), py::arg("stream_rows"), py::arg("rows"),
       py::arg("seq_len"), py::arg("max_segs"), py::arg("seg_offsets"), py::arg("seg_src"), py::arg("row_start"),
       py::arg("row_end"), py::arg("counts"), py::arg("scratch"), py::arg("stream"));
+  m.def(
+      "token_mix_order",
+      [](int mode, uintptr_t idx, int64_t base, std::vector<uint64_t> keys, uint64_t n_domain, uint32_t half_bits,
+         int64_t n_corpus, std::vector<int64_t> cbase, std::vector<int64_t> doc_lo, std::vector<int64_t> n_docs,
+         std::vector<int64_t> full_span, bool inner_shuffle, std::vector<std::vector<uint64_t>> inner_keys,
+         std::vector<uint32_t> inner_half_bits, int64_t n, uintptr_t order, uintptr_t stream) {
+        const size_t parts = doc_lo.size();
+        if (parts < 1 || parts > static_cast<size_t>(ddl::kMixMaxParts) || cbase.size() != parts + 1 ||
+            n_docs.size() != parts || full_span.size() != parts)
+          throw std::invalid_argument("token_mix_order: unsupported arguments (1..16 parts, cbase of parts + 1)");
+        if (inner_shuffle && (inner_keys.size() != parts || inner_half_bits.size() != parts))
+          throw std::invalid_argument("token_mix_order: unsupported arguments (inner keys of every part)");
+        ddl::MixOrderSpec sp{};
+        sp.ri = make_index(mode, idx, base, keys, n_domain, half_bits);
+        sp.parts = static_cast<int32_t>(parts);
+        sp.inner_shuffle = inner_shuffle ? 1 : 0;
+        sp.n_corpus = n_corpus;
+        for (size_t p = 0; p < parts; ++p) {
+          sp.cbase[p] = cbase[p];
+          sp.part[p] = ddl::MixPart{doc_lo[p], n_docs[p], full_span[p]};
+          if (inner_shuffle)
+            sp.keys[p] = make_keys(inner_keys[p], n_docs[p] > 0 ? static_cast<uint64_t>(n_docs[p]) : 0,
+                                   inner_half_bits[p]);
+        }
+        sp.cbase[parts] = cbase[parts];
+        sp.n = n;
+        sp.order = as_ptr<int64_t>(order);
+        check_rc(ddl::token_mix_order(sp, as_stream(stream)), "token_mix_order");
+      },
+      py::arg("mode"), py::arg("idx"), py::arg("base"), py::arg("keys"), py::arg("n_domain"), py::arg("half_bits"),
+      py::arg("n_corpus"), py::arg("cbase"), py::arg("doc_lo"), py::arg("n_docs"), py::arg("full_span"),
+      py::arg("inner_shuffle"), py::arg("inner_keys"), py::arg("inner_half_bits"), py::arg("n"), py::arg("order"),
+      py::arg("stream"));
+  m.attr("MIX_MAX_PARTS") = ddl::kMixMaxParts;
   m.attr("TOKEN_SEG_LDS_CAP") = ddl::kTiSegCap;
   m.attr("RAGGED_MAP_CAP") = ddl::kRaggedMapCap;
   m.def(

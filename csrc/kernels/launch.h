@@ -7,6 +7,7 @@
 #include <stdint.h>
 
 #include "common.h"
+#include "tokens_mix.h"
 
 namespace ddl {
 
@@ -248,6 +249,27 @@ struct StreamRowsSpec {
   int64_t* scratch;     // [4 * rows] int64 of device memory between the two launches
 };
 int token_stream_plan_rows(const StreamRowsSpec& spec, hipStream_t st);
+
+// tokens_mix.hip ------------------------------------------------------------
+// The document order of one epoch of a weighted mixture of corpus parts (tokens_mix.h has the definition):
+// order[i], i < n, is a corpus document id, a document of part p appearing floor(repeat_p) or one more times. The
+// order is what token_stream_table and the two stream plans take as an explicit index (RowIndex mode 1, n =
+// the order's length). One launch, one thread and one 8-byte store per entry; the whole spec travels as the kernel's
+// argument, nothing is uploaded. ri: the epoch's permutation of [0, n) (mode 2, base 0), the identity, or an
+// explicit index of n values; inner_shuffle != 0: keys[p] is part p's fixed permutation of its n_docs documents
+// (checked for every part with extra documents), 0: the identity.
+struct MixOrderSpec {
+  RowIndex ri;
+  int32_t parts;
+  int32_t inner_shuffle;
+  int64_t n_corpus;
+  int64_t cbase[kMixMaxParts + 1];
+  MixPart part[kMixMaxParts];
+  FeistelKeys keys[kMixMaxParts];
+  int64_t n;       // entries of the order = cbase[parts]
+  int64_t* order;  // out: [n], device
+};
+int token_mix_order(const MixOrderSpec& spec, hipStream_t st);
 
 // ragged.hip ----------------------------------------------------------------
 // Device twin of the host gather_ragged: sequence i (src_start[i] elements into src, dst_offsets[i + 1] -

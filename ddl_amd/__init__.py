@@ -22,6 +22,7 @@ __all__ = [
     "ZeroCopyTokenLoader",
     "ResidentTokenLoader",
     "ResidentTokenStreamLoader",
+    "TokenMix",
     "DataLoader",
     "OutputSpec",
     "StagingSpec",
@@ -36,6 +37,7 @@ from .datasetwrapper import ProducerFunctionSkeleton
 from .parallel.launcher import distributed_dataloader, start
 from .permutation import EpochOrder, FeistelPermutation
 from .specs import OrderSpec, OutputSpec, StagingSpec
+from .token_mix import TokenMix
 from .types import DDLEnv, Marker
 
 

@@ -1298,6 +1298,26 @@ def _stream_lengths(offs: np.ndarray, q: np.ndarray) -> np.ndarray:
     return np.maximum(offs[q + 1] - offs[q], 0) if q.size else np.zeros(0, dtype=np.int64)
 
 
+def _host_order(order, perm) -> np.ndarray | None:
+    """An ``order=`` argument as a flat int64 array on the host (None: not given)."""
+    if order is None:
+        return None
+    if perm is not None:
+        raise ValueError("give either order or perm, not both")
+    q = order.detach().cpu().numpy() if isinstance(order, torch.Tensor) else np.asarray(order)
+    if q.dtype != np.int64:
+        raise TypeError("order must be int64")
+    return np.ascontiguousarray(q.reshape(-1))
+
+
+def _order_lengths(offs: np.ndarray, q: np.ndarray) -> np.ndarray:
+    """Lengths of the documents of an explicit order; an id outside the corpus is an empty document, as in the
+    kernels."""
+    inside = (q >= 0) & (q < offs.size - 1)
+    qc = np.where(inside, q, 0)
+    return np.where(inside, _stream_lengths(offs, qc), 0) if q.size else np.zeros(0, dtype=np.int64)
+
+
 def _stream_default_segs(n: int, rows: int, seq_len: int, shuffled_rows: bool = False) -> int:
     """A capacity that needs no length: every document that touches a window holds one of its tokens. Shuffled
     rows: every row may cut a document at either end, and a segment holds at least one token."""
@@ -1350,7 +1370,8 @@ def _stream_row_select(row_perm, row_index, row_base: int, rows: int) -> np.ndar
 
 def ref_stream_tokens(corpus: torch.Tensor, corpus_offsets, *, perm=None, row_base: int, rows: int, seq_len: int,
                       pad_id: int = 0, position_dtype=torch.int64, max_segs: int | None = None, labels: bool = False,
-                      ignore_index: int = -100, row_perm: FeistelPermutation | None = None, row_index=None) -> dict:
+                      ignore_index: int = -100, row_perm: FeistelPermutation | None = None, row_index=None,
+                      order=None) -> dict:
     """The definition of the token stream format, in NumPy on the CPU (no plan code is involved)::
 
         stream = concat(corpus[offs[q_i] : offs[q_i + 1]] for i in range(n)),  q_i = perm(i) (or i),  T = len(stream)
@@ -1378,15 +1399,25 @@ def ref_stream_tokens(corpus: torch.Tensor, corpus_offsets, *, perm=None, row_ba
     ``(rho_k + 1) * S > T`` (the partial last row and everything past it) makes the batch invalid, reported like
     an overflow (``n_rows`` = -1, every row padding, ``cu_seqlens`` all zero, labels all ``ignore_index``) with
     ``n_seg``, ``n_tokens`` and ``max_seg`` taken over the valid rows only; a valid batch has ``counts`` =
-    ``[rows, n_seg, rows * S, max_seg]``. ``max_segs`` None: ``min(min(n, rows * S) + 2 * rows, rows * S)``."""
+    ``[rows, n_seg, rows * S, max_seg]``. ``max_segs`` None: ``min(min(n, rows * S) + 2 * rows, rows * S)``.
+
+    ``order`` (int64 array or tensor of corpus document ids, any length, repeats allowed; not together with
+    ``perm``) gives the documents themselves: ``q_i = order[i]``, ``n = len(order)``. A segment belongs to a position
+    of the order, not to a corpus id: two neighbouring copies of one document are two segments. An id outside the
+    corpus is an empty document. This is how a ``TokenMix`` epoch is defined: ``order = ref_mix_order(...)``."""
     S, R, base = int(seq_len), int(rows), int(row_base)
     if S <= 0 or R < 1 or base < 0:
         raise ValueError("seq_len must be > 0, rows >= 1 and row_base >= 0")
     rho = _stream_row_select(row_perm, row_index, base, R)
     offs = torch.as_tensor(corpus_offsets).to("cpu", torch.int64).reshape(-1).numpy()
-    n = offs.size - 1
-    q = _stream_order(n, perm)
-    lens = _stream_lengths(offs, q)
+    q = _host_order(order, perm)
+    if q is None:
+        n = offs.size - 1
+        q = _stream_order(n, perm)
+        lens = _stream_lengths(offs, q)
+    else:
+        n = q.size
+        lens = _order_lengths(offs, q)
     table = np.concatenate([np.zeros(1, dtype=np.int64), np.cumsum(lens, dtype=np.int64)])
     M = _stream_default_segs(n, R, S, rho is not None) if max_segs is None else int(max_segs)
     if rho is None:
@@ -1434,28 +1465,42 @@ def ref_stream_tokens(corpus: torch.Tensor, corpus_offsets, *, perm=None, row_ba
 
 
 def token_stream_table(corpus_offsets: torch.Tensor, perm: FeistelPermutation | None = None,
-                       out: torch.Tensor | None = None, stream=None, scratch: torch.Tensor | None = None):
+                       out: torch.Tensor | None = None, stream=None, scratch: torch.Tensor | None = None,
+                       order=None):
     """``table`` (int64 [n + 1]) of the token stream of an epoch: ``table[i]`` = the tokens in front of document
     ``i`` of the order (``perm``, or the identity), ``table[n]`` = the stream's length. Device offsets: the
     ``token_stream_table`` kernels (a three-launch device-wide scan with the permutation evaluated inline: no
     n-sized index, no host step); ``out``: an int64 device tensor of n + 1 entries, ``scratch``: one of
-    ``_native.hip().token_stream_table_scratch(n)``, else allocated here. CPU offsets: NumPy."""
+    ``_native.hip().token_stream_table_scratch(n)``, else allocated here. CPU offsets: NumPy.
+
+    ``order`` (not together with ``perm``): the table of an explicit order of corpus document ids (an int64 tensor
+    on the offsets' device, or an array for CPU offsets), of any length ``n = len(order)``, repeats allowed."""
     if not isinstance(corpus_offsets, torch.Tensor) or corpus_offsets.dtype != torch.int64:
         raise TypeError("corpus_offsets must be an int64 tensor")
     offs = corpus_offsets.reshape(-1)
     if offs.numel() < 1 or not offs.is_contiguous():
         raise ValueError("corpus_offsets must be contiguous and hold at least one entry")
-    n = offs.numel() - 1
+    n_corpus = n = offs.numel() - 1
     if perm is not None and perm.n != n:
         raise IndexError("the permutation's domain is not the corpus")
+    if order is not None and perm is not None:
+        raise ValueError("give either order or perm, not both")
     if not offs.is_cuda:
         o = offs.numpy()
-        t = np.concatenate([np.zeros(1, dtype=np.int64), np.cumsum(_stream_lengths(o, _stream_order(n, perm)))])
+        if order is not None:
+            q = _host_order(order, None)
+            n, lens = q.size, _order_lengths(o, q)
+        else:
+            lens = _stream_lengths(o, _stream_order(n, perm))
+        t = np.concatenate([np.zeros(1, dtype=np.int64), np.cumsum(lens)])
         t = torch.from_numpy(t.astype(np.int64))
         if out is not None:
             out[:n + 1].copy_(t)
             return out[:n + 1]
         return t
+    if order is not None:
+        order = _device_order(order, offs.device)
+        n = order.numel()
     h = _native.hip()
     handle, stream = _stream_pair(stream, offs.device)
     need = h.token_stream_table_scratch(n)
@@ -1467,10 +1512,19 @@ def token_stream_table(corpus_offsets: torch.Tensor, perm: FeistelPermutation | 
     for name, t, size in (("out", out, n + 1), ("scratch", scratch, need)):
         if t.dtype != torch.int64 or t.device != offs.device or not t.is_contiguous() or t.numel() < size:
             raise ValueError(f"{name} must be a contiguous int64 tensor of >= {size} entries on the offsets' device")
-    h.token_stream_table(corpus_offsets=offs.data_ptr(), n_corpus=n, n=n, table=out.data_ptr(),
+    h.token_stream_table(corpus_offsets=offs.data_ptr(), n_corpus=n_corpus, n=n, table=out.data_ptr(),
                          tile_sums=scratch.data_ptr(), stream=handle,
-                         **(_index_kw(None, perm, 0) if n else _index_kw(None, None, 0)))
+                         **(_index_kw(order, perm, 0) if n else _index_kw(None, None, 0)))
     return out[:n + 1]
+
+
+def _device_order(order, dev) -> torch.Tensor:
+    """An ``order=`` argument of the GPU ops: a flat, contiguous int64 tensor on ``dev``."""
+    if not isinstance(order, torch.Tensor) or order.dtype != torch.int64:
+        raise TypeError("order must be an int64 tensor")
+    if order.device != dev or not order.is_contiguous():
+        raise ValueError("order must be a contiguous tensor on the corpus's device")
+    return order.reshape(-1)
 
 
 def token_stream_bytes(rows: int, seq_len: int, max_segs: int, position_dtype=torch.int64,
@@ -1524,20 +1578,22 @@ def _launch_stream_emit(h, whole: torch.Tensor, plan: tuple, *, corpus_ptr: int,
 def launch_stream_plan(plan_ptr: int, whole: torch.Tensor, *, corpus_ptr: int, corpus_elems: int, tok16: bool,
                        corpus_offsets_ptr: int, n_corpus: int, table_ptr: int, selector: dict, row_base: int,
                        rows: int, seq_len: int, pad_id: int, max_segs: int, position_dtype=torch.int64,
-                       stream: int = 0, labels: bool = False, ignore_index: int = -100) -> dict:
+                       stream: int = 0, labels: bool = False, ignore_index: int = -100,
+                       n: int | None = None) -> dict:
     """The two launches of one token stream batch on raw stream ``stream``: ``token_stream_plan`` and
     ``pad_pack_tokens_indexed`` (pack mode, counts read from device memory). ``plan_ptr`` / ``whole``: the two
     sizes of ``token_stream_bytes``, 16-byte aligned device memory; ``selector``: the ``RowIndex`` of the epoch's
-    order with base 0, the one ``table_ptr``'s table was built with. Nothing here allocates, copies or
-    synchronises. Returns the dict of ``stream_tokens_indexed_device``."""
+    order with base 0, the one ``table_ptr``'s table was built with; ``n``: the order's length where it is not the
+    corpus's document count (an explicit order). Nothing here allocates, copies or synchronises. Returns the dict of
+    ``stream_tokens_indexed_device``."""
     h = _native.hip()
     S, R, M = int(seq_len), int(rows), int(max_segs)
     ignore_index = check_ignore_index(labels, ignore_index)
     plan = _stream_plan_layout(plan_ptr, R, M)
     o_ss, o_so, o_rs, o_re, _ = plan
-    plan_kw = dict(table=table_ptr, corpus_offsets=corpus_offsets_ptr, n_corpus=n_corpus, n=n_corpus,
-                   row_base=int(row_base), rows=R, seq_len=S, max_segs=M, seg_offsets=o_so, seg_src=o_ss,
-                   row_start=o_rs, row_end=o_re, stream=stream, **selector)
+    plan_kw = dict(table=table_ptr, corpus_offsets=corpus_offsets_ptr, n_corpus=n_corpus,
+                   n=n_corpus if n is None else int(n), row_base=int(row_base), rows=R, seq_len=S, max_segs=M,
+                   seg_offsets=o_so, seg_src=o_ss, row_start=o_rs, row_end=o_re, stream=stream, **selector)
     return _launch_stream_emit(h, whole, plan, corpus_ptr=corpus_ptr, corpus_elems=corpus_elems, tok16=tok16, rows=R,
                                seq_len=S, pad_id=pad_id, max_segs=M, position_dtype=position_dtype, stream=stream,
                                labels=labels, ignore_index=ignore_index, plan_fn=h.token_stream_plan, plan_kw=plan_kw)
@@ -1547,21 +1603,22 @@ def launch_stream_plan_rows(plan_ptr: int, whole: torch.Tensor, *, corpus_ptr: i
                             corpus_offsets_ptr: int, n_corpus: int, table_ptr: int, selector: dict,
                             row_selector: dict, stream_rows: int, rows: int, seq_len: int, pad_id: int,
                             max_segs: int, position_dtype=torch.int64, stream: int = 0, labels: bool = False,
-                            ignore_index: int = -100) -> dict:
+                            ignore_index: int = -100, n: int | None = None) -> dict:
     """``launch_stream_plan`` for rows picked anywhere in the stream: the two launches of ``token_stream_plan_rows``
     and ``pad_pack_tokens_indexed``, the call it is for contiguous rows. ``plan_ptr``: the plan size of
     ``token_stream_bytes(..., shuffled_rows=True)``; ``row_selector``: the ``RowIndex`` arguments that select the
     batch's rows (``_index_kw`` of a device ``row_index``, or of ``row_perm`` at the batch's first position);
-    ``stream_rows``: the stream's full rows, ``T // seq_len``. Nothing here allocates, copies or synchronises."""
+    ``stream_rows``: the stream's full rows, ``T // seq_len``; ``n``: as for ``launch_stream_plan``. Nothing here
+    allocates, copies or synchronises."""
     h = _native.hip()
     S, R, M = int(seq_len), int(rows), int(max_segs)
     ignore_index = check_ignore_index(labels, ignore_index)
     plan = _stream_plan_layout(plan_ptr, R, M)
     o_ss, o_so, o_rs, o_re, o_scr = plan
-    plan_kw = dict(table=table_ptr, corpus_offsets=corpus_offsets_ptr, n_corpus=n_corpus, n=n_corpus,
-                   stream_rows=int(stream_rows), rows=R, seq_len=S, max_segs=M, seg_offsets=o_so, seg_src=o_ss,
-                   row_start=o_rs, row_end=o_re, scratch=o_scr, stream=stream, **selector,
-                   **{"rows_" + k: v for k, v in row_selector.items()})
+    plan_kw = dict(table=table_ptr, corpus_offsets=corpus_offsets_ptr, n_corpus=n_corpus,
+                   n=n_corpus if n is None else int(n), stream_rows=int(stream_rows), rows=R, seq_len=S, max_segs=M,
+                   seg_offsets=o_so, seg_src=o_ss, row_start=o_rs, row_end=o_re, scratch=o_scr, stream=stream,
+                   **selector, **{"rows_" + k: v for k, v in row_selector.items()})
     return _launch_stream_emit(h, whole, plan, corpus_ptr=corpus_ptr, corpus_elems=corpus_elems, tok16=tok16, rows=R,
                                seq_len=S, pad_id=pad_id, max_segs=M, position_dtype=position_dtype, stream=stream,
                                labels=labels, ignore_index=ignore_index, plan_fn=h.token_stream_plan_rows,
@@ -1573,7 +1630,8 @@ def stream_tokens_indexed_device(corpus: torch.Tensor, corpus_offsets: torch.Ten
                                  pad_id: int = 0, max_segs: int | None = None, position_dtype=torch.int64,
                                  labels: bool = False, ignore_index: int = -100, out: torch.Tensor | None = None,
                                  stream=None, row_perm: FeistelPermutation | None = None,
-                                 row_index: torch.Tensor | None = None, stream_rows: int | None = None) -> dict:
+                                 row_index: torch.Tensor | None = None, stream_rows: int | None = None,
+                                 order: torch.Tensor | None = None) -> dict:
     """Rows ``[row_base, row_base + rows)`` of the token stream (``ref_stream_tokens``, the definition) out of a
     corpus in HBM: ``corpus`` (flat int32 / 16-bit ids), ``corpus_offsets`` (int64 [n + 1]) and ``table``
     (``token_stream_table`` of the same ``perm``) are device tensors. Two launches -- ``token_stream_plan`` and
@@ -1590,10 +1648,19 @@ def stream_tokens_indexed_device(corpus: torch.Tensor, corpus_offsets: torch.Ten
     ``token_stream_plan_rows`` (two launches) in front of the same emit launch; ``out`` then holds
     ``sum(token_stream_bytes(..., shuffled_rows=True))`` bytes and ``max_segs`` None is ``min(min(n, rows * seq_len)
     + 2 * rows, rows * seq_len)``. ``stream_rows``: the stream's full rows ``T // seq_len``, the domain ``row_perm``
-    must have; None with ``row_perm`` on the GPU reads ``table[n]`` back, the one synchronising step here."""
+    must have; None with ``row_perm`` on the GPU reads ``table[n]`` back, the one synchronising step here.
+
+    ``order`` (not together with ``perm``): an int64 tensor of corpus document ids on the corpus's device, of any
+    length, repeats allowed (``token_mix_order`` writes one): the documents of the stream themselves, ``n =
+    len(order)``, and ``table`` is ``token_stream_table(order=...)`` of it, ``n + 1`` entries."""
     flat, offs, _ = _device_plan_args(corpus, corpus_offsets, None, None, 0, 0, seq_len, position_dtype)
     ignore_index = check_ignore_index(labels, ignore_index)
-    S, R, n = int(seq_len), int(rows), offs.numel() - 1
+    S, R, n_corpus = int(seq_len), int(rows), offs.numel() - 1
+    if order is not None and perm is not None:
+        raise ValueError("give either order or perm, not both")
+    if order is not None:
+        order = _device_order(order, flat.device) if flat.is_cuda else torch.from_numpy(_host_order(order, None))
+    n = n_corpus if order is None else int(order.numel())
     if R < 1 or int(row_base) < 0:
         raise ValueError("rows must be >= 1 and row_base >= 0")
     if R * S > 0x7FFFFFFF:
@@ -1609,11 +1676,11 @@ def stream_tokens_indexed_device(corpus: torch.Tensor, corpus_offsets: torch.Ten
     if not flat.is_cuda:
         if row_perm is not None:
             o = offs.numpy()
-            _check_row_perm(row_perm, int(np.maximum(np.diff(o), 0).sum()) // S if stream_rows is None
-                            else int(stream_rows), row_base, R)
+            lens = np.maximum(np.diff(o), 0) if order is None else _order_lengths(o, order.numpy())
+            _check_row_perm(row_perm, int(lens.sum()) // S if stream_rows is None else int(stream_rows), row_base, R)
         return ref_stream_tokens(flat, offs, perm=perm, row_base=row_base, rows=R, seq_len=S, pad_id=pad_id,
                                  position_dtype=position_dtype, max_segs=M, labels=labels, ignore_index=ignore_index,
-                                 row_perm=row_perm, row_index=row_index)
+                                 row_perm=row_perm, row_index=row_index, order=order)
     if (not isinstance(table, torch.Tensor) or table.dtype != torch.int64 or table.device != flat.device
             or not table.is_contiguous() or table.numel() < n + 1):
         raise ValueError("table must be a contiguous int64 tensor of n + 1 entries on the corpus's device "
@@ -1636,14 +1703,83 @@ def stream_tokens_indexed_device(corpus: torch.Tensor, corpus_offsets: torch.Ten
     with torch.cuda.stream(stream):
         buf = _token_out_buffer(out, plan_b + batch_b, flat.device)
     common = dict(corpus_ptr=flat.data_ptr(), corpus_elems=flat.numel(), tok16=flat.dtype in _TOK16,
-                  corpus_offsets_ptr=offs.data_ptr(), n_corpus=n, table_ptr=table.data_ptr(),
-                  selector=_index_kw(None, perm, 0) if n else _index_kw(None, None, 0), rows=R, seq_len=S,
+                  corpus_offsets_ptr=offs.data_ptr(), n_corpus=n_corpus, n=n, table_ptr=table.data_ptr(),
+                  selector=_index_kw(order, perm, 0) if n else _index_kw(None, None, 0), rows=R, seq_len=S,
                   pad_id=pad_id, max_segs=M, position_dtype=position_dtype, stream=handle, labels=labels,
                   ignore_index=ignore_index)
     if by_rows:
         return launch_stream_plan_rows(buf.data_ptr(), buf[plan_b:], row_selector=row_selector,
                                        stream_rows=0 if stream_rows is None else int(stream_rows), **common)
     return launch_stream_plan(buf.data_ptr(), buf[plan_b:], row_base=int(row_base), **common)
+
+
+def ref_mix_order(mix, *, seed: int, epoch: int, shuffle: bool = True) -> np.ndarray:
+    """The definition of a ``TokenMix`` epoch's document order, in NumPy: int64 ``[mix.n_order]`` corpus ids.
+
+    With ``b`` = ``mix.bounds``, ``n_p``, ``full_p``, ``k_p`` and ``cbase`` as ``TokenMix`` defines them and ``N'`` =
+    ``mix.n_order``::
+
+        v = phi_e(i)                        phi_e = FeistelPermutation(N', seed, epoch), or the identity
+        p: cbase[p] <= v < cbase[p + 1]     j = v - cbase[p]
+        order[i] = b[p] + j % n_p                           if j < full_p * n_p      (the whole passes)
+                 = b[p] + sigma_p(j - full_p * n_p)         otherwise                (the k_p extra documents)
+
+    ``sigma_p = FeistelPermutation(n_p, part_seed_for(seed, p), 0)``, or the identity without ``shuffle``: it does
+    not depend on the epoch, so a part's extra documents are the same set in every epoch and every epoch has the
+    same token count."""
+    n = int(mix.n_order)
+    pos = np.arange(n, dtype=np.int64)
+    v = np.asarray(FeistelPermutation(n, int(seed), int(epoch))(pos), dtype=np.int64) if shuffle else pos
+    cbase = np.asarray(mix.cbase, dtype=np.int64)
+    p = np.searchsorted(cbase[1:], v, side="right")  # the parts whose entries end at or before v
+    j = v - cbase[p]
+    n_docs = np.asarray(mix.n_docs, dtype=np.int64)
+    span = np.asarray(mix.full, dtype=np.int64) * n_docs
+    lo = np.asarray(mix.bounds[:-1], dtype=np.int64)
+    whole = j < span[p]
+    order = lo[p] + np.where(whole, j % n_docs[p], 0)
+    for part in range(mix.parts):
+        at = np.flatnonzero(~whole & (p == part))
+        if at.size:
+            r = j[at] - span[part]
+            order[at] = lo[part] + (np.asarray(mix.inner_perm(seed, part)(r), dtype=np.int64) if shuffle else r)
+    return order
+
+
+def token_mix_order(mix, *, seed: int, epoch: int, shuffle: bool = True, device=None,
+                    out: torch.Tensor | None = None, stream=None) -> torch.Tensor:
+    """``ref_mix_order`` as an int64 tensor on ``device`` (default: ``out``'s, else the CPU). On the GPU the
+    ``token_mix_order`` kernel writes it: one launch, one thread per entry, the whole mix travelling as the kernel's
+    argument, no copy and no synchronisation. ``out``: a contiguous int64 tensor of at least ``mix.n_order`` entries
+    to write into (the result is its first ``n_order``), else allocated here."""
+    n = int(mix.n_order)
+    dev = out.device if out is not None else torch.device("cpu" if device is None else device)
+    if out is not None and (out.dtype != torch.int64 or not out.is_contiguous() or out.numel() < n
+                            or (device is not None and torch.device(device).type != dev.type)):
+        raise ValueError(f"out must be a contiguous int64 tensor of >= {n} entries on the given device")
+    if dev.type != "cuda":
+        order = torch.from_numpy(ref_mix_order(mix, seed=seed, epoch=epoch, shuffle=shuffle))
+        if out is None:
+            return order
+        out.reshape(-1)[:n].copy_(order)
+        return out.reshape(-1)[:n]
+    h = _native.hip()
+    if dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    handle, stream = _stream_pair(stream, dev)
+    if out is None:
+        with torch.cuda.stream(stream):
+            out = torch.empty(n, dtype=torch.int64, device=dev)
+    launch_mix_order(h, out.data_ptr(), mix.device_args(seed, shuffle), n_corpus=mix.n_documents, n=n,
+                     perm=FeistelPermutation(n, int(seed), int(epoch)) if shuffle else None, stream=handle)
+    return out.reshape(-1)[:n]
+
+
+def launch_mix_order(h, order_ptr: int, parts: dict, *, n_corpus: int, n: int, perm, stream: int) -> None:
+    """The one launch of ``token_mix_order`` on raw stream ``stream``: ``parts`` = ``TokenMix.device_args`` (it does
+    not change with the epoch), ``perm`` = the epoch's permutation of the ``n`` entries or None."""
+    h.token_mix_order(n_corpus=int(n_corpus), n=int(n), order=order_ptr, stream=stream, **parts,
+                      **_index_kw(None, perm, 0))
 
 
 def _check_row_perm(row_perm: FeistelPermutation, stream_rows: int, row_base: int, rows: int) -> None:

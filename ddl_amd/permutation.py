@@ -70,6 +70,17 @@ def row_seed_for(seed: int) -> int:
     return _mix64_int((int(seed) ^ _ROW_SEED_SALT) & _MASK64) & ((1 << 63) - 1)
 
 
+_PART_SEED_SALT = 0x6D69785F70617274  # "mix_part"
+
+
+def part_seed_for(seed: int, part: int) -> int:
+    """The seed of part ``part``'s fixed inner permutation in a ``TokenMix`` (which documents of the part make its
+    fractional repeat), derived from the loader's ``seed`` like ``row_seed_for`` with a salt of its own and the
+    part's number mixed in: ``mix64((seed ^ salt) + (part + 1) * golden)`` reduced to 63 bits."""
+    z = ((int(seed) ^ _PART_SEED_SALT) + (int(part) + 1) * 0x9E3779B97F4A7C15) & _MASK64
+    return _mix64_int(z) & ((1 << 63) - 1)
+
+
 def half_bits_for(n: int) -> int:
     if n <= 0:
         raise ValueError("permutation domain must be positive")

@@ -31,6 +31,15 @@ rows dropped at the epoch's end are a different set each epoch. The batches stay
 same at every world size. ``token_stream_plan_rows`` (two launches, one wave per row) takes the place of
 ``token_stream_plan``, the emit launch is the same: three launches per step, and two more cached selectors per
 epoch on the host.
+
+``mix=TokenMix(bounds, repeat)`` weights parts of the corpus by document order: the epoch's order is then
+``ops.ref_mix_order`` -- ``N'`` entries, a document of part ``p`` appearing ``floor(repeat[p])`` or one more times --
+instead of a permutation of the corpus, and everything above holds with ``order_e[i]`` in the place of
+``perm_e(i)``. Two neighbouring copies of a document are two segments. Once per epoch ``token_mix_order`` writes the
+order into one of two int64 buffers of ``N'`` entries (next to the two tables, on the prep stream, in front of the
+table scan), and the table, plan and emit kernels read it as an explicit index: still no copy, no host read of
+device memory and no synchronisation. The extra documents of a fractional repeat are the same in every epoch
+(``token_mix``), which keeps ``total_tokens``, the rows and batches per epoch and the checkpoint cursor constant.
 """
 
 from __future__ import annotations
@@ -42,10 +51,11 @@ from . import _native
 from .corpus_replica import ResidentCorpusLoader
 from .exceptions import DDLError
 from .models.tokens import SharedTokenSource
-from .ops.kernels import (check_ignore_index, launch_stream_plan, launch_stream_plan_rows, ref_stream_tokens,
-                          stream_max_segments, token_stream_bytes)
+from .ops.kernels import (check_ignore_index, launch_mix_order, launch_stream_plan, launch_stream_plan_rows,
+                          ref_mix_order, ref_stream_tokens, row_selector, stream_max_segments, token_stream_bytes)
 from .permutation import FeistelPermutation, row_seed_for
 from .resident import STATE_VERSION, PrefetchedIndexedLoader
+from .token_mix import TokenMix
 from .types import DDLEnv
 from .utils import streams
 
@@ -64,12 +74,17 @@ class ResidentTokenStreamLoader(ResidentCorpusLoader, PrefetchedIndexedLoader):
                  device: str | torch.device | None = None, n_epochs: int | None = None,
                  resume_state: dict | None = None, handoff: str = "device", hbm_fraction: float = 0.8,
                  chunk_bytes: int = 256 << 20, max_segments: int | None = None, labels: bool = False,
-                 ignore_index: int = -100, shuffle_rows: bool = False):
+                 ignore_index: int = -100, shuffle_rows: bool = False, mix: TokenMix | None = None):
         """``global_batch`` counts rows. ``max_segments``: the capacity of a batch's ``cu_seqlens`` (default
         ``ops.stream_max_segments``, which no window of any order exceeds; a smaller one that a batch overflows
         gives that batch as padding with ``n_rows`` = -1). ``shuffle_rows``: the rows of an epoch in the order of
         a second permutation (see the module's text); ``shuffle=False`` with it gives shuffled rows of the
-        unshuffled stream."""
+        unshuffled stream. ``mix``: a ``TokenMix`` over all the corpus's documents (``mix.bounds[-1] ==
+        n_documents``): the epoch's documents are its weighted order. The extra documents of a fractional repeat
+        are the same in every epoch, so ``total_tokens`` -- the tokens of one epoch, computed here once -- and
+        with it the rows and batches per epoch and the checkpoint cursor are constants; the default
+        ``max_segments`` is ``ops.stream_max_segments`` over the lengths with every document counted
+        ``mix.max_copies`` times, a multiset that holds every epoch's documents."""
         if handoff not in ("device", "host"):
             raise ValueError("handoff must be 'device' or 'host'")
         self.labels, self.ignore_index = bool(labels), check_ignore_index(labels, ignore_index)
@@ -90,8 +105,17 @@ class ResidentTokenStreamLoader(ResidentCorpusLoader, PrefetchedIndexedLoader):
         offs = self._offs_t.numpy()
         lens = np.maximum(np.diff(offs), 0)
         self.n_documents, self.total_tokens = int(source.n), int(lens.sum())
+        self.mix = mix
+        if mix is not None:
+            if not isinstance(mix, TokenMix):
+                raise TypeError("mix must be a TokenMix")
+            if mix.n_documents != self.n_documents:
+                raise ValueError(f"the mix covers {mix.n_documents} documents, the corpus has {self.n_documents}")
+            self.total_tokens = mix.epoch_tokens(lens, int(seed), bool(shuffle))
+            lens = np.repeat(lens, mix.document_copies())
+        self.n_order = mix.n_order if mix is not None else self.n_documents
         if self.total_tokens < self.GB * self.seq_len:
-            raise ValueError(f"the corpus holds {self.total_tokens} tokens, fewer than one global batch of "
+            raise ValueError(f"an epoch holds {self.total_tokens} tokens, fewer than one global batch of "
                              f"{self.GB} x {self.seq_len}")
         self.order = _RowOrder(self.total_tokens // self.seq_len, self.GB, int(seed), bool(shuffle))
         self.shuffle_rows = bool(shuffle_rows)
@@ -107,24 +131,29 @@ class ResidentTokenStreamLoader(ResidentCorpusLoader, PrefetchedIndexedLoader):
         self.nbytes = int(offs[-1]) * source.token_bytes if source.n else 0
         self.n_elems = self.nbytes // source.token_bytes
         self.prep_stream = streams.batch_stream(self.device) if self.device.type == "cuda" else None
-        self.tables_built = 0
+        self.tables_built = self.orders_built = 0
+        self._epoch_evs: list = []
         self._windows: list = []
         if not self._attach_replica(hbm_fraction, chunk_bytes):
             return
         try:
-            n = self.n_documents
+            n = self.n_order
             scratch = _native.hip().token_stream_table_scratch(n)
-            table_bytes = 8 * (2 * (n + 1) + scratch)
+            table_bytes = 8 * (2 * (n + 1) + scratch + (2 * n if mix is not None else 0))
             free, _ = torch.cuda.mem_get_info(self.device)
             if table_bytes > float(hbm_fraction) * free:
-                raise DDLError(f"the two epoch tables ({table_bytes} bytes) exceed hbm_fraction={hbm_fraction} of "
-                               f"the free HBM ({free} bytes free)")
+                raise DDLError(f"the two epoch tables{' and orders' if mix is not None else ''} ({table_bytes} bytes) "
+                               f"exceed hbm_fraction={hbm_fraction} of the free HBM ({free} bytes free)")
             self._replica.offsets(self._offs_t, self.prep_stream)
             with streams.on_stream(self.prep_stream):
                 # two tables: prefetch crosses the epoch boundary (epoch e lives in slot e % 2)
                 self._tables = [torch.empty(n + 1, dtype=torch.int64, device=self.device) for _ in range(2)]
                 self._scratch = torch.empty(scratch, dtype=torch.int64, device=self.device)
                 self._table_epoch = [None, None]
+                if mix is not None:  # the epochs' document orders, slot for slot with the tables
+                    self._orders = [torch.empty(n, dtype=torch.int64, device=self.device) for _ in range(2)]
+                    self._order_sel = [row_selector(o) for o in self._orders]
+                    self._mix_args = mix.device_args(self.seed, self.order.shuffle)
                 self._plan_bytes, self._batch_bytes = token_stream_bytes(self.LB, self.seq_len, self.max_segments,
                                                                          labels=self.labels,
                                                                          shuffled_rows=self.shuffle_rows)
@@ -138,18 +167,44 @@ class ResidentTokenStreamLoader(ResidentCorpusLoader, PrefetchedIndexedLoader):
     def _perm(self, epoch: int) -> FeistelPermutation | None:
         return FeistelPermutation(self.n_documents, self.seed, epoch) if self.order.shuffle else None
 
+    def _mix_perm(self, epoch: int) -> FeistelPermutation | None:
+        return FeistelPermutation(self.n_order, self.seed, epoch) if self.order.shuffle else None
+
     def _row_perm(self, epoch: int) -> FeistelPermutation | None:
         return FeistelPermutation(self.order.n_samples, self.row_seed, epoch) if self.shuffle_rows else None
 
+    def _order(self, epoch: int) -> np.ndarray | None:
+        """The CPU twin's document order of a mix (None without one: ``_perm`` is the order)."""
+        if self.mix is None:
+            return None
+        return ref_mix_order(self.mix, seed=self.seed, epoch=epoch, shuffle=self.order.shuffle)
+
+    def _doc_selector(self, epoch: int) -> dict:
+        """The ``RowIndex`` of the epoch's documents: its permutation, or the slot's order buffer of a mix."""
+        return self._selector(epoch) if self.mix is None else self._order_sel[epoch % 2]
+
     def _table(self, epoch: int, sel: dict) -> torch.Tensor:
-        """Epoch ``epoch``'s table, built on the prep stream the first time a step of the epoch
-        is assembled. The slot's earlier epoch is two behind: every step that reads it was enqueued before."""
+        """Epoch ``epoch``'s table (behind its order, with a mix), built on the prep stream the first time a step
+        of the epoch is assembled. The slot's earlier epoch is two behind: every step that reads it was enqueued
+        before."""
         k = epoch % 2
         if self._table_epoch[k] != epoch:
+            timed = self.profile_every > 0
+            if timed:  # the epoch's launches between two timing events (``timing``)
+                evs = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                evs[0].record(self.prep_stream)
+            if self.mix is not None:
+                launch_mix_order(_native.hip(), self._orders[k].data_ptr(), self._mix_args,
+                                 n_corpus=self.n_documents, n=self.n_order, perm=self._mix_perm(epoch),
+                                 stream=self.prep_stream.cuda_stream)
+                self.orders_built += 1
             _native.hip().token_stream_table(
-                corpus_offsets=self._replica.offsets_dev.data_ptr(), n_corpus=self.n_documents, n=self.n_documents,
+                corpus_offsets=self._replica.offsets_dev.data_ptr(), n_corpus=self.n_documents, n=self.n_order,
                 table=self._tables[k].data_ptr(), tile_sums=self._scratch.data_ptr(),
                 stream=self.prep_stream.cuda_stream, **sel)
+            if timed:
+                evs[1].record(self.prep_stream)
+                self._epoch_evs.append(evs)
             self._table_epoch[k] = epoch
             self.tables_built += 1
         return self._tables[k]
@@ -159,12 +214,13 @@ class ResidentTokenStreamLoader(ResidentCorpusLoader, PrefetchedIndexedLoader):
         row_base = g * self.GB + self.rank * self.LB
         st = self.prep_stream
         if st is None:  # the CPU twin: the definition itself
-            r = ref_stream_tokens(self._toks, self._offs_t, perm=self._perm(e), row_base=row_base, rows=self.LB,
-                                  seq_len=self.seq_len, pad_id=self.pad_id, max_segs=self.max_segments,
-                                  labels=self.labels, ignore_index=self.ignore_index, row_perm=self._row_perm(e))
+            r = ref_stream_tokens(self._toks, self._offs_t, perm=self._perm(e) if self.mix is None else None,
+                                  row_base=row_base, rows=self.LB, seq_len=self.seq_len, pad_id=self.pad_id,
+                                  max_segs=self.max_segments, labels=self.labels, ignore_index=self.ignore_index,
+                                  row_perm=self._row_perm(e), order=self._order(e))
             ev = None
         else:
-            sel = self._selector(e)
+            sel = self._doc_selector(e)
             table = self._table(e, sel)
 
             def issue(win, whole):
@@ -172,7 +228,7 @@ class ResidentTokenStreamLoader(ResidentCorpusLoader, PrefetchedIndexedLoader):
                 common = dict(
                     corpus_ptr=rep.hbm.data_ptr(), corpus_elems=self.n_elems,
                     tok16=self.source.token_bytes == 2, corpus_offsets_ptr=rep.offsets_dev.data_ptr(),
-                    n_corpus=self.n_documents, table_ptr=table.data_ptr(), selector=sel,
+                    n_corpus=self.n_documents, n=self.n_order, table_ptr=table.data_ptr(), selector=sel,
                     rows=self.LB, seq_len=self.seq_len, pad_id=self.pad_id, max_segs=self.max_segments,
                     stream=st.cuda_stream, labels=self.labels, ignore_index=self.ignore_index)
                 if self.shuffle_rows:
@@ -205,15 +261,20 @@ class ResidentTokenStreamLoader(ResidentCorpusLoader, PrefetchedIndexedLoader):
             "shuffle_rows": self.shuffle_rows,
             "row_seed": self.row_seed,
             "world_size": self.W,
+            "mix": None if self.mix is None else self.mix.state(),
+            "n_order": self.n_order,
         }
 
     def _apply_state(self, sd: dict) -> None:
         if sd.get("kind") != "token_stream" or sd.get("version") != STATE_VERSION:
             raise ValueError(f"not a token stream loader state (kind={sd.get('kind')!r}): rows of the token stream "
                              "and batches of sequences do not share a cursor")
+        mix_state = None if self.mix is None else self.mix.state()
+        if sd.get("mix") != mix_state:  # a state without the key: no mix; before total_tokens, which a mix changes
+            raise ValueError(f"checkpoint mix={sd.get('mix')} does not match {mix_state}")
         for key, mine in (("global_batch", self.GB), ("seq_len", self.seq_len), ("n_documents", self.n_documents),
                           ("total_tokens", self.total_tokens), ("order_seed", self.seed),
-                          ("shuffle", self.order.shuffle)):
+                          ("shuffle", self.order.shuffle), ("n_order", self.n_order)):
             if sd.get(key) is not None and sd[key] != mine:
                 raise ValueError(f"checkpoint {key}={sd[key]} does not match {mine}")
         if bool(sd.get("shuffle_rows", False)) != self.shuffle_rows:  # a state without the key: contiguous rows
@@ -231,7 +292,20 @@ class ResidentTokenStreamLoader(ResidentCorpusLoader, PrefetchedIndexedLoader):
                 "load_gbps": self.nbytes / self.load_s / 1e9 if self.load_s > 0 else 0.0, "handoff": self.handoff,
                 "host_waits": self.host_waits, "replica_shared": self.replica_shared, "format": "stream",
                 "rows_per_epoch": self.order.n_samples, "max_segments": self.max_segments,
-                "tables_built": self.tables_built, "shuffle_rows": self.shuffle_rows}
+                "tables_built": self.tables_built, "shuffle_rows": self.shuffle_rows,
+                "mix_parts": self.mix.parts if self.mix is not None else 0, "mix_documents": self.n_order,
+                "orders_built": self.orders_built}
+
+    def timing(self) -> dict:
+        """``ResidentCorpusLoader.timing`` and ``epoch_prep_us``: the mean device time of an epoch's own launches
+        (``token_mix_order`` with a mix, and the table scan) over the epochs begun while ``profile_every`` > 0."""
+        out = super().timing()
+        evs = self._epoch_evs
+        out["epoch_prep_us"], out["epoch_prep_samples"] = None, len(evs)
+        if evs:
+            self.prep_stream.synchronize()
+            out["epoch_prep_us"] = 1e3 * sum(a.elapsed_time(b) for a, b in evs) / len(evs)
+        return out
 
     def close(self) -> None:
         if getattr(self, "prep_stream", None) is not None:
@@ -240,7 +314,7 @@ class ResidentTokenStreamLoader(ResidentCorpusLoader, PrefetchedIndexedLoader):
             self._queue.clear()
         self._kernel_evs = []
         self._windows = []
-        self._tables = self._scratch = None
+        self._tables = self._scratch = self._orders = None
         self._release_replica()
 
     def __del__(self):  # pragma: no cover - best effort

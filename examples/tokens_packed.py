@@ -38,6 +38,9 @@ full (100% dense, static shapes) and a segment is a run of one document inside o
 each batch's plan are built on the GPU; the checkpoint is ``kind="token_stream"``. ``--shuffle-rows`` adds the
 sample shuffle of that format (Megatron's ``shuffle_idx``): a step's rows are drawn from all over the epoch's
 stream by a second permutation, so the pieces of a long document no longer sit in neighbouring rows of one step.
+``--mix 2,1,0.5`` weights parts of the corpus (``ddl_amd.TokenMix``): the documents are cut into as many equal
+parts as there are numbers, and a document of part ``p`` appears ``repeat[p]`` times per epoch (a fraction: that
+share of the part's documents once more, the same ones every epoch).
 
 ``--labels`` (with ``--resident`` or ``--zero-copy``) asks the loader for the next-token targets as well
 (``labels=True``: int64 ``labels``, ``-100`` where a position has no target -- the end of a row or of a segment,
@@ -76,6 +79,8 @@ def main() -> None:
                          "(--global-batch counts rows)")
     ap.add_argument("--shuffle-rows", action="store_true",
                     help="with --resident --stream: the epoch's rows in a shuffled order (shuffle_rows=True)")
+    ap.add_argument("--mix", default=None, metavar="R0,R1,...",
+                    help="with --resident --stream: repeats of equal parts of the corpus, e.g. 2,1,0.5 (TokenMix)")
     ap.add_argument("--labels", action="store_true",
                     help="with --resident or --zero-copy: the loader also delivers next-token labels, and every "
                          "batch runs a tiny embedding -> linear -> cross_entropy step on them")
@@ -91,6 +96,8 @@ def main() -> None:
         ap.error("--stream is a format of --resident (packed rows by construction; it has no --device-plan mode)")
     if a.shuffle_rows and not a.stream:
         ap.error("--shuffle-rows is an option of --resident --stream")
+    if a.mix and not a.stream:
+        ap.error("--mix is an option of --resident --stream")
     if a.labels and not (a.zero_copy or a.resident):
         ap.error("--labels needs --resident or --zero-copy (the producer path does not deliver labels)")
     vocab = a.vocab or (512 if a.labels else 50257)
@@ -111,8 +118,16 @@ def main() -> None:
                 src = SharedTokenSource(SharedArraySource(name + "_tok", n_tok, (1,), "int32"), offs, a.seq_len)
             pack_order = "ffd" if a.mode == "pack" else "in_order"
             if a.stream:
+                mix = None
+                if a.mix:  # equal parts of the corpus, by document index
+                    repeat = [float(r) for r in a.mix.split(",")]
+                    bounds = [round(p * a.n_seqs / len(repeat)) for p in range(len(repeat) + 1)]
+                    mix = ddl_amd.TokenMix(bounds, repeat)
                 dl = ddl_amd.ResidentTokenStreamLoader(src, a.global_batch, a.seq_len, env, n_epochs=a.epochs,
-                                                       shuffle_rows=a.shuffle_rows, **lab_kw)
+                                                       shuffle_rows=a.shuffle_rows, mix=mix, **lab_kw)
+                if mix is not None and env.rank == 0:
+                    print(f"mix: {mix.parts} parts x {list(mix.repeat)} -> {mix.n_order} documents and "
+                          f"{dl.total_tokens} tokens per epoch (the corpus: {a.n_seqs} documents)", flush=True)
             elif a.resident and a.device_plan:  # first-fit-decreasing is a host plan
                 dl = ddl_amd.ResidentTokenLoader(src, a.global_batch, a.seq_len, a.mode, env, n_epochs=a.epochs,
                                                  plan="device", **lab_kw)
