@@ -998,7 +998,7 @@ PYBIND11_MODULE(_ddl_hip, m) {
       "column_stats",
       [](uintptr_t src, int64_t n, int64_t cols, uintptr_t sum, uintptr_t sumsq, uintptr_t mn, uintptr_t mx,
          uintptr_t stream) {
-        check_rc(ddl::column_stats(as_ptr<const float>(src), n, cols, as_ptr<float>(sum), as_ptr<float>(sumsq),
+        check_rc(ddl::column_stats(as_ptr<const float>(src), n, cols, as_ptr<double>(sum), as_ptr<double>(sumsq),
                                    as_ptr<float>(mn), as_ptr<float>(mx), as_stream(stream)),
                  "column_stats");
       },

@@ -320,9 +320,9 @@ int checksum_words(const void* ptr, int64_t bytes, uint64_t* out, uint64_t* scra
 // life of the accumulator); checksum_finalize adds sum(partials) into *out.
 int checksum_accumulate(const void* ptr, int64_t bytes, uint64_t* partials, int64_t n_partials, hipStream_t st);
 int checksum_finalize(const uint64_t* partials, int64_t n_partials, uint64_t* out, hipStream_t st);
-// Per-column sum / sum of squares / min / max of an [n, cols] f32 matrix
-// (reference harness normalisation stats, tests/run_ddl.py:45-77).
-int column_stats(const float* src, int64_t n, int64_t cols, float* out_sum, float* out_sumsq, float* out_min,
+// Per-column sum / sum of squares (float64, accumulated onto zeroed outputs) and min / max (float32, onto
+// +inf / -inf) of an [n, cols] f32 matrix (reference harness normalisation stats, tests/run_ddl.py:45-77).
+int column_stats(const float* src, int64_t n, int64_t cols, double* out_sum, double* out_sumsq, float* out_min,
                  float* out_max, hipStream_t st);
 
 }  // namespace ddl

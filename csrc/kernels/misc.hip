@@ -1,7 +1,10 @@
 // Reductions used by the loader: batch checksums (debug exactly-once mode and
 // the bench consumer step, which must read every delivered byte) and
 // per-column statistics (the reference harness's min-max / standard
-// normalisation, tests/run_ddl.py:45-77).
+// normalisation, tests/run_ddl.py:45-77). The statistics
+// kernels produce float64 sums and sums of squares and exact float32 min / max;
+// mean and std are formed from them in float64 by the caller (ops.column_stats),
+// never by a float32 sumsq/n - mean^2.
 //
 // Pattern (guide App. B "Reduction"): 16 B loads per lane, per-wave shuffle
 // reduction over 64 lanes, per-block LDS reduction, one atomic per block.
@@ -83,92 +86,122 @@ __global__ void __launch_bounds__(kThreads) checksum_final_kernel(const uint64_t
   }
 }
 
+// Column statistics. Sums and sums of squares are carried in float64 from the first add to the last: every
+// input is widened as it is loaded (its square is then exact), each thread accumulates its share in float64
+// registers, the block combines them through LDS in float64 and adds one float64 atomic per (block, column)
+// and quantity. The caller forms mean = sum/n and var = sumsq/n - mean^2 in float64, where the subtraction
+// keeps ~1e-16 * (mean/std)^2 relative accuracy; in float32 a column at mean/std = 1e3 loses its variance.
+// min / max stay float32 (exact): one integer atomic per (block, column), signed for non-negative bit
+// patterns and unsigned for negative ones, on outputs pre-set to +inf / -inf.
+__device__ __forceinline__ void atomic_min_max_f32(float* mn, float* mx, float lo, float hi) {
+  const int lo_i = __float_as_int(lo), hi_i = __float_as_int(hi);
+  if (lo_i >= 0)
+    atomicMin(reinterpret_cast<int*>(mn), lo_i);
+  else
+    atomicMax(reinterpret_cast<unsigned int*>(mn), static_cast<unsigned int>(lo_i));
+  if (hi_i >= 0)
+    atomicMax(reinterpret_cast<int*>(mx), hi_i);
+  else
+    atomicMin(reinterpret_cast<unsigned int*>(mx), static_cast<unsigned int>(hi_i));
+}
+
+constexpr int kStatsLoads = 8;  // independent 4 B loads in flight per lane
+
+// One thread's running statistics of one column.
+struct ColumnAcc {
+  double s = 0., q = 0.;
+  float lo = INFINITY, hi = -INFINITY;
+  __device__ __forceinline__ void add(float v) {
+    const double d = v;
+    s += d;
+    q = fma(d, d, q);
+    lo = fminf(lo, v);
+    hi = fmaxf(hi, v);
+  }
+  __device__ __forceinline__ void merge(const ColumnAcc& o) {
+    s += o.s;
+    q += o.q;
+    lo = fminf(lo, o.lo);
+    hi = fmaxf(hi, o.hi);
+  }
+};
+
 // Narrow matrices (cols <= 256): flat, coalesced grid-stride over elements
 // with a per-thread stride that is a multiple of `cols`, so every thread
 // always lands on the same column and accumulates it in registers (no idle
 // lanes, no strided loads). Per-column partials are then combined through LDS
 // and one atomic per (block, column).
-template <int kMaxCols>
 __global__ void __launch_bounds__(kThreads) column_stats_narrow_kernel(const float* __restrict__ src, int64_t total,
-                                                                       int cols, float* sum, float* sumsq, float* mn,
+                                                                       int cols, double* sum, double* sumsq, float* mn,
                                                                        float* mx) {
-  __shared__ float ps[kMaxCols], pq[kMaxCols];
-  for (int c = threadIdx.x; c < cols; c += kThreads) {
-    ps[c] = 0.f;
-    pq[c] = 0.f;
-  }
-  __syncthreads();
   const int active = (kThreads / cols) * cols;  // threads per block that take part
   const int64_t stride = static_cast<int64_t>(gridDim.x) * active;  // multiple of cols
-  float s = 0.f, q = 0.f, lo = INFINITY, hi = -INFINITY;
+  ColumnAcc a[2];  // two dependency chains
   if (threadIdx.x < active) {
     int64_t e = static_cast<int64_t>(blockIdx.x) * active + threadIdx.x;
-    for (; e + 3 * stride < total; e += 4 * stride) {  // 4 independent loads in flight per lane
-      const float v0 = src[e], v1 = src[e + stride], v2 = src[e + 2 * stride], v3 = src[e + 3 * stride];
-      s += (v0 + v1) + (v2 + v3);
-      q = fmaf(v0, v0, fmaf(v1, v1, fmaf(v2, v2, fmaf(v3, v3, q))));
-      lo = fminf(lo, fminf(fminf(v0, v1), fminf(v2, v3)));
-      hi = fmaxf(hi, fmaxf(fmaxf(v0, v1), fmaxf(v2, v3)));
+    for (; e + (kStatsLoads - 1) * stride < total; e += kStatsLoads * stride) {  // independent loads in flight
+      float v[kStatsLoads];
+#pragma unroll
+      for (int k = 0; k < kStatsLoads; ++k) v[k] = src[e + k * stride];
+#pragma unroll
+      for (int k = 0; k < kStatsLoads; ++k) a[k & 1].add(v[k]);
     }
-    for (; e < total; e += stride) {
-      const float v = src[e];
-      s += v;
-      q = fmaf(v, v, q);
-      lo = fminf(lo, v);
-      hi = fmaxf(hi, v);
-    }
-    const int c = static_cast<int>((static_cast<int64_t>(blockIdx.x) * active + threadIdx.x) % cols);
-    atomicAdd(&ps[c], s);  // LDS atomics: cheap, few threads per column
-    atomicAdd(&pq[c], q);
+    for (; e < total; e += stride) a[0].add(src[e]);
   }
-  __syncthreads();
-  // min/max through a second LDS pass (float atomics on LDS for min/max are not native)
+  a[0].merge(a[1]);
+  const double s = a[0].s, q = a[0].q;
+  const float lo = a[0].lo, hi = a[0].hi;
+  // per-column combine through LDS: idle threads hold the neutral element
+  __shared__ double red_s[kThreads], red_q[kThreads];
   __shared__ float red_lo[kThreads], red_hi[kThreads];
-  red_lo[threadIdx.x] = threadIdx.x < active ? lo : INFINITY;
-  red_hi[threadIdx.x] = threadIdx.x < active ? hi : -INFINITY;
+  red_s[threadIdx.x] = s;
+  red_q[threadIdx.x] = q;
+  red_lo[threadIdx.x] = lo;
+  red_hi[threadIdx.x] = hi;
   __syncthreads();
   const int64_t b0 = static_cast<int64_t>(blockIdx.x) * active;
   for (int c = threadIdx.x; c < cols; c += kThreads) {
+    double cs = 0., cq = 0.;
     float l = INFINITY, h = -INFINITY;
     // threads t with (b0 + t) % cols == c
     const int first = static_cast<int>(((c - b0 % cols) % cols + cols) % cols);
     for (int t = first; t < active; t += cols) {
+      cs += red_s[t];
+      cq += red_q[t];
       l = fminf(l, red_lo[t]);
       h = fmaxf(h, red_hi[t]);
     }
-    atomicAdd(sum + c, ps[c]);
-    atomicAdd(sumsq + c, pq[c]);
-    const int li = __float_as_int(l), hi_i = __float_as_int(h);
-    if (li >= 0)
-      atomicMin(reinterpret_cast<int*>(mn + c), li);
-    else
-      atomicMax(reinterpret_cast<unsigned int*>(mn + c), static_cast<unsigned int>(li));
-    if (hi_i >= 0)
-      atomicMax(reinterpret_cast<int*>(mx + c), hi_i);
-    else
-      atomicMin(reinterpret_cast<unsigned int*>(mx + c), static_cast<unsigned int>(hi_i));
+    atomicAdd(sum + c, cs);
+    atomicAdd(sumsq + c, cq);
+    atomic_min_max_f32(mn + c, mx + c, l, h);
   }
 }
 
 // Wide matrices: one block per 64-column tile x row slice; lanes = columns.
 __global__ void __launch_bounds__(kThreads) column_stats_wide_kernel(const float* __restrict__ src, int64_t n,
-                                                                     int64_t cols, float* sum, float* sumsq, float* mn,
+                                                                     int64_t cols, double* sum, double* sumsq, float* mn,
                                                                      float* mx, int64_t rows_per_block) {
   const int64_t c = static_cast<int64_t>(blockIdx.y) * 64 + (threadIdx.x & 63);
   const int wave = threadIdx.x >> 6;
   const int64_t r0 = static_cast<int64_t>(blockIdx.x) * rows_per_block;
   const int64_t r1 = r0 + rows_per_block < n ? r0 + rows_per_block : n;
-  float s = 0.f, q = 0.f, lo = INFINITY, hi = -INFINITY;
+  ColumnAcc a[2];
   if (c < cols) {
-    for (int64_t r = r0 + wave; r < r1; r += kWaves) {
-      const float v = src[r * cols + c];
-      s += v;
-      q = fmaf(v, v, q);
-      lo = fminf(lo, v);
-      hi = fmaxf(hi, v);
+    int64_t r = r0 + wave;
+    for (; r + (kStatsLoads - 1) * kWaves < r1; r += kStatsLoads * kWaves) {
+      float v[kStatsLoads];
+#pragma unroll
+      for (int k = 0; k < kStatsLoads; ++k) v[k] = src[(r + k * kWaves) * cols + c];
+#pragma unroll
+      for (int k = 0; k < kStatsLoads; ++k) a[k & 1].add(v[k]);
     }
+    for (; r < r1; r += kWaves) a[0].add(src[r * cols + c]);
   }
-  __shared__ float ps[kWaves][64], pq[kWaves][64], pl[kWaves][64], ph[kWaves][64];
+  a[0].merge(a[1]);
+  double s = a[0].s, q = a[0].q;
+  float lo = a[0].lo, hi = a[0].hi;
+  __shared__ double ps[kWaves][64], pq[kWaves][64];
+  __shared__ float pl[kWaves][64], ph[kWaves][64];
   const int lane = threadIdx.x & 63;
   ps[wave][lane] = s;
   pq[wave][lane] = q;
@@ -184,15 +217,7 @@ __global__ void __launch_bounds__(kThreads) column_stats_wide_kernel(const float
     }
     atomicAdd(sum + c, s);
     atomicAdd(sumsq + c, q);
-    const int lo_i = __float_as_int(lo), hi_i = __float_as_int(hi);
-    if (lo_i >= 0)
-      atomicMin(reinterpret_cast<int*>(mn + c), lo_i);
-    else
-      atomicMax(reinterpret_cast<unsigned int*>(mn + c), static_cast<unsigned int>(lo_i));
-    if (hi_i >= 0)
-      atomicMax(reinterpret_cast<int*>(mx + c), hi_i);
-    else
-      atomicMin(reinterpret_cast<unsigned int*>(mx + c), static_cast<unsigned int>(hi_i));
+    atomic_min_max_f32(mn + c, mx + c, lo, hi);
   }
 }
 
@@ -252,7 +277,7 @@ __global__ void __launch_bounds__(kThreads) touch_pages_kernel(const uint8_t* __
 }  // namespace
 
 int touch_pages(const void* ptr, int64_t bytes, int64_t page, uint32_t* sink, int blocks, hipStream_t st) {
-  if (bytes <= 0) return 0;
+  if (bytes < 4) return 0;  // no whole 4 B word in the range: nothing to read
   if (page < 4 || page % 4 != 0 || reinterpret_cast<uintptr_t>(ptr) % 4 != 0 || blocks < 1) return -2;
   const int64_t n_pages = (bytes - 4) / page + 1;  // every page start inside [ptr, ptr + bytes - 4]
   hipLaunchKernelGGL(touch_pages_kernel, dim3(static_cast<uint32_t>(blocks)), dim3(kThreads), 0, st,
@@ -297,7 +322,7 @@ int checksum_finalize(const uint64_t* partials, int64_t n_partials, uint64_t* ou
   return static_cast<int>(hipGetLastError());
 }
 
-int column_stats(const float* src, int64_t n, int64_t cols, float* out_sum, float* out_sumsq, float* out_min,
+int column_stats(const float* src, int64_t n, int64_t cols, double* out_sum, double* out_sumsq, float* out_min,
                  float* out_max, hipStream_t st) {
   if (n <= 0 || cols <= 0) return 0;
   if (cols <= 256) {
@@ -306,7 +331,7 @@ int column_stats(const float* src, int64_t n, int64_t cols, float* out_sum, floa
     int64_t blocks = (total + kThreads * 16 - 1) / (kThreads * 16);
     if (blocks > 256) blocks = 256;
     if (blocks < 1) blocks = 1;
-    hipLaunchKernelGGL(column_stats_narrow_kernel<256>, dim3(static_cast<uint32_t>(blocks)), dim3(kThreads), 0, st,
+    hipLaunchKernelGGL(column_stats_narrow_kernel, dim3(static_cast<uint32_t>(blocks)), dim3(kThreads), 0, st,
                        src, total, static_cast<int>(cols), out_sum, out_sumsq, out_min, out_max);
     return static_cast<int>(hipGetLastError());
   }

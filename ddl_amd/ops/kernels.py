@@ -16,6 +16,7 @@ csrc/kernels/common.h): output row ``r`` reads source row
 from __future__ import annotations
 
 import dataclasses
+import functools
 import math
 from typing import Sequence
 
@@ -1889,21 +1890,40 @@ def normalize_columns(x: torch.Tensor, mode: str = "standard", out_dtype=None, s
 
 
 def column_stats(x: torch.Tensor, stream=None) -> dict[str, torch.Tensor]:
-    """Per-column sum / sumsq / min / max / mean / std of an [N, C] f32 matrix."""
+    """Per-column sum / sumsq / min / max / mean / std (population) of an [N, C] f32 matrix, as float32 tensors.
+
+    The sums and sums of squares are accumulated in float64 (on the GPU by the kernels, from the first add on),
+    and ``mean = sum/n`` and ``std = sqrt(sumsq/n - mean^2)`` are formed from them in float64 before the one
+    rounding to float32: a column whose mean is 1e3 or 1e4 times its spread keeps its std, which a float32
+    ``sumsq/n - mean^2`` loses. ``sum`` and ``sumsq`` are the float64 totals rounded to float32; ``min`` and
+    ``max`` are exact."""
     if x.dim() != 2 or x.dtype != torch.float32:
         raise TypeError("column_stats expects [N, C] float32")
     n, c = x.shape
     if not x.is_cuda:
-        s, q = x.double().sum(0).float(), (x.double() ** 2).sum(0).float()
+        xd = x.double()
+        acc = torch.zeros((4, c), dtype=torch.float64)
+        acc[0], acc[1] = xd.sum(0), (xd * xd).sum(0)
         mn, mx = x.min(0).values, x.max(0).values
     else:
         x = x.contiguous()
-        s = torch.zeros(c, dtype=torch.float32, device=x.device)
-        q = torch.zeros_like(s)
-        mn = torch.full_like(s, float("inf"))
-        mx = torch.full_like(s, float("-inf"))
-        _native.hip().column_stats(src=x.data_ptr(), n=n, cols=c, sum=s.data_ptr(), sumsq=q.data_ptr(),
-                                   min=mn.data_ptr(), max=mx.data_ptr(), stream=_stream_handle(stream))
-    mean = s / n
-    var = (q / n - mean * mean).clamp_min(0)
-    return {"sum": s, "sumsq": q, "min": mn, "max": mx, "mean": mean, "std": var.sqrt()}
+        buf = _column_stats_init(c, x.device).clone()  # one launch sets up every accumulator
+        acc = buf[:8 * c].view(torch.float64).view(4, c)  # sum, sumsq, and room for mean, std
+        mn, mx = buf[8 * c:9 * c], buf[9 * c:]
+        base = buf.data_ptr()
+        _native.hip().column_stats(src=x.data_ptr(), n=n, cols=c, sum=base, sumsq=base + 8 * c, min=base + 32 * c,
+                                   max=base + 36 * c, stream=_stream_handle(stream))
+    torch.div(acc[:2], n, out=acc[2:])  # float64 mean and mean of squares
+    torch.addcmul(acc[3], acc[2], acc[2], value=-1, out=acc[3]).clamp_min_(0).sqrt_()
+    s, q, mean, std = acc.float().unbind(0)
+    return {"sum": s, "sumsq": q, "min": mn, "max": mx, "mean": mean, "std": std}
+
+
+@functools.lru_cache(maxsize=64)
+def _column_stats_init(c: int, device: torch.device) -> torch.Tensor:
+    """The start state of ``column_stats``'s accumulators for ``c`` columns, as one float32 buffer: 8c zeros (a
+    float64 [4, c]), c times +inf (min), c times -inf (max). Built on the host, so that it is complete on the
+    device whichever stream clones it first."""
+    t = torch.zeros(10 * c, dtype=torch.float32)
+    t[8 * c:9 * c], t[9 * c:] = float("inf"), float("-inf")
+    return t.to(device)
