@@ -194,6 +194,7 @@ int launch_hwc(void* dst, int32_t out_dt, const void* src, int64_t batch, int64_
   if constexpr (sizeof(Tin) == 1) {
     if (channels == 3 && (out_dt == kBF16 || out_dt == kF32)) {
       const int64_t tiles3 = (pixels + kPix3 - 1) / kPix3;
+      if (batch * tiles3 >= (int64_t{1} << 32)) return -4;  // as below: one block per (image, tile)
       const dim3 grid3(static_cast<uint32_t>(batch * tiles3));
       if (out_dt == kBF16)
         hipLaunchKernelGGL(hwc3_u8_to_chw_kernel<1>, grid3, dim3(kThreads), 0, st, dst,

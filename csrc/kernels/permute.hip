@@ -320,11 +320,15 @@ int flat_grid_capped(int64_t work, int64_t max_blocks) {
 }
 
 template <typename U>
-void launch_move(void* dst, const void* src, int64_t n_rows, int64_t row_bytes, const RowIndex& ri, int scatter,
-                 bool nt_loads, int64_t max_blocks, hipStream_t st) {
+int launch_move(void* dst, const void* src, int64_t n_rows, int64_t row_bytes, const RowIndex& ri, int scatter,
+                bool nt_loads, int64_t max_blocks, hipStream_t st) {
   const int64_t units = row_bytes / static_cast<int64_t>(sizeof(U));
   if (units >= kThreads) {
     const int64_t chunks = (units + kThreads * kUnroll - 1) / (kThreads * kUnroll);
+    // move_rows_chunked divides the tile number in 32 bits. gather_rows' bound on n_rows * row_elems does not
+    // imply this one: chunks <= units / 256 only gives n_tiles < 2^40 * (element size / unit size) / 256, and
+    // e.g. 2^30 rows of 513 int64 (1026 4-byte units, 2 chunks) pass that bound with 2^31 tiles.
+    if (n_rows * chunks >= (int64_t{1} << 31)) return -4;
     auto kernel = nt_loads ? move_rows_chunked<U, true> : move_rows_chunked<U, false>;
     hipLaunchKernelGGL(kernel, tile_grid(n_rows * chunks, max_blocks), dim3(kThreads), 0, st,
                        static_cast<uint8_t*>(dst), static_cast<const uint8_t*>(src), units, chunks, n_rows * chunks,
@@ -334,6 +338,7 @@ void launch_move(void* dst, const void* src, int64_t n_rows, int64_t row_bytes, 
                        static_cast<uint8_t*>(dst), static_cast<const uint8_t*>(src), units, n_rows * units, ri,
                        scatter);
   }
+  return static_cast<int>(hipGetLastError());
 }
 
 template <typename Tin, typename Tout>
@@ -386,19 +391,19 @@ int gather_rows(void* dst, int32_t out_dt, const void* src, int32_t in_dt, int64
   if (n_rows <= 0 || row_elems <= 0) return 0;
   const int scatter = flags & 1;
   const bool nt = (flags & (1 | kHostSource)) == 0;  // a device-source gather: non-temporal source loads
-  // the chunked kernels index tiles and in-row elements with 32-bit arithmetic
+  // the chunked kernels index tiles and in-row elements with 32-bit arithmetic. The converting ones take rows of
+  // >= 2048 elements in chunks of >= 8192, so chunks <= row_elems / 2048 and their tiles stay below 2^29 under
+  // this bound; the raw moves' tile count depends on the unit width and is checked in launch_move.
   if (n_rows >= (int64_t{1} << 31) || n_rows * row_elems >= (int64_t{1} << 40)) return -4;
   const bool same = (out_dt == in_dt) && !aff.enabled;
   if (same) {
     const int64_t row_bytes = row_elems * dtype_size(in_dt);
     const uintptr_t align = reinterpret_cast<uintptr_t>(dst) | reinterpret_cast<uintptr_t>(src);
     if (row_bytes % 16 == 0 && align % 16 == 0)
-      launch_move<u32x4>(dst, src, n_rows, row_bytes, ri, scatter, nt, max_blocks, st);
-    else if (row_bytes % 4 == 0 && align % 4 == 0)
-      launch_move<uint32_t>(dst, src, n_rows, row_bytes, ri, scatter, nt, max_blocks, st);
-    else
-      launch_move<uint8_t>(dst, src, n_rows, row_bytes, ri, scatter, nt, max_blocks, st);
-    return static_cast<int>(hipGetLastError());
+      return launch_move<u32x4>(dst, src, n_rows, row_bytes, ri, scatter, nt, max_blocks, st);
+    if (row_bytes % 4 == 0 && align % 4 == 0)
+      return launch_move<uint32_t>(dst, src, n_rows, row_bytes, ri, scatter, nt, max_blocks, st);
+    return launch_move<uint8_t>(dst, src, n_rows, row_bytes, ri, scatter, nt, max_blocks, st);
   }
   if (scatter) return -2;  // converting scatters are not needed by the loader
   if (row_elems >= (int64_t{1} << 31) || (aff.enabled && aff.plane >= (int64_t{1} << 31))) return -4;

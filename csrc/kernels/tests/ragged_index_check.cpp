@@ -5,6 +5,7 @@
 // dst_offsets[n] elements, so a unit outside the hulls or an element outside the destination is a heap
 // overflow. The result is compared with a plain per-sequence memcpy, and every destination element must
 // be written exactly once.
+#include <limits.h>
 #include <string.h>
 
 #include "../ragged_index.h"
@@ -126,10 +127,84 @@ void run_all() {
   run_case<T>("all empty", {0, 0, 3}, {0, 1, 0}, 0, 1);
 }
 
+// Far case: no memory behind the addresses, the index arithmetic alone, at a source address and sequence starts
+// whose byte offsets pass 2^33. Every unit a lane would load must be 16-byte aligned and inside the sequence's hull,
+// every surviving element must be the one at a + p * eb, and each position of each sequence must come exactly once.
+template <typename T>
+void far_case(const char* name, uint64_t src, const std::vector<int64_t>& src_start, const std::vector<int64_t>& lens) {
+  ++g_cases;
+  constexpr int eb = static_cast<int>(sizeof(T));
+  constexpr int per_unit = ddl::kRgUnitBytes / eb;
+  const int64_t n = static_cast<int64_t>(lens.size());
+  std::vector<int64_t> dst_offsets(n + 1, 0);
+  for (int64_t i = 0; i < n; ++i) dst_offsets[i + 1] = dst_offsets[i] + lens[i];
+  std::vector<int32_t> tile_start(n + 1);
+  const int64_t n_tiles = ddl::ragged_tile_plan(src, src_start.data(), dst_offsets.data(), n, eb, tile_start.data());
+  if (n_tiles < 0) return fail(name, "a plan that fits int32 is refused");
+  std::vector<int> written(dst_offsets[n], 0);
+  for (int64_t tile = 0; tile < n_tiles; ++tile) {
+    const int64_t seq = ddl::rg_find_seq([&](int64_t j) { return tile_start[j]; }, n, tile);
+    if (seq < 0 || seq >= n || tile < tile_start[seq] || tile >= tile_start[seq + 1]) return fail(name, "tile map");
+    const int64_t chunk = tile - tile_start[seq];
+    const int64_t d0 = dst_offsets[seq], len = dst_offsets[seq + 1] - d0;
+    const uint64_t a = src + static_cast<uint64_t>(src_start[seq]) * eb;
+    if ((a - src) / eb != static_cast<uint64_t>(src_start[seq])) return fail(name, "sequence address wrapped");
+    const int64_t units = ddl::rg_units(a, len, eb);
+    const int64_t head = ddl::rg_head_elems(a, eb);
+    const uint64_t hull_lo = a & ~uint64_t{15}, hull_hi = (a + static_cast<uint64_t>(len) * eb + 15) & ~uint64_t{15};
+    for (int tid = 0; tid < ddl::kRgThreads; ++tid)
+      for (int k = 0; k < ddl::kRgUnroll; ++k) {
+        const int64_t u = ddl::rg_unit(chunk, k, tid);
+        if (u >= units) continue;
+        const uint64_t ua = ddl::rg_unit_addr(a, u);
+        if (ua % 16 || ua < hull_lo || ua + 16 > hull_hi) return fail(name, "unit outside the hull");
+        for (int e = 0; e < per_unit; ++e) {
+          const int64_t p = ddl::rg_elem_pos(u, e, head, eb);
+          if (p < 0 || p >= len) continue;
+          if (ua + static_cast<uint64_t>(e) * eb != a + static_cast<uint64_t>(p) * eb) return fail(name, "element address");
+          ++written[d0 + p];
+        }
+      }
+  }
+  for (int w : written)
+    if (w != 1) return fail(name, "a position is not produced exactly once");
+}
+
+template <typename T>
+void run_far() {
+  constexpr int64_t eb = static_cast<int64_t>(sizeof(T));
+  const int64_t far = (int64_t{1} << 33) / eb;  // the element at byte 2^33
+  for (uint64_t shift : {0, 1, 3}) {
+    const uint64_t src = (uint64_t{0x7f} << 40) + shift * eb;  // a plausible mapping address, element-aligned only
+    far_case<T>("far starts", src, {far - 3, far + 5000, (int64_t{1} << 40) + 1, (int64_t{1} << 31) / eb - 1, 2 * far + 7},
+                {5000, 0, 17, 9000, 1});
+  }
+  // ragged_tile_plan at its int32 limit: INT32_MAX tiles are accepted, one more is refused
+  const int64_t per_tile = ddl::kRgTileUnits * (ddl::kRgUnitBytes / eb);  // elements per tile of an aligned sequence
+  const uint64_t src = uint64_t{1} << 44;
+  {
+    ++g_cases;
+    const std::vector<int64_t> start = {0, int64_t{INT32_MAX} * per_tile};
+    std::vector<int64_t> dofs = {0, int64_t{INT32_MAX} * per_tile, int64_t{INT32_MAX} * per_tile};
+    std::vector<int32_t> ts(3);
+    if (ddl::ragged_tile_plan(src, start.data(), dofs.data(), 2, eb, ts.data()) != INT32_MAX || ts[1] != INT32_MAX ||
+        ts[2] != INT32_MAX)
+      fail("tile plan limit", "INT32_MAX tiles are not accepted");
+    dofs[2] += 1;  // one more element: one more tile
+    if (ddl::ragged_tile_plan(src, start.data(), dofs.data(), 2, eb, ts.data()) != -1)
+      fail("tile plan limit", "2^31 tiles are not refused");
+    dofs = {0, int64_t{INT32_MAX} * per_tile + 1, int64_t{INT32_MAX} * per_tile + 1};  // one sequence alone past it
+    if (ddl::ragged_tile_plan(src, start.data(), dofs.data(), 1, eb, ts.data()) != -1)
+      fail("tile plan limit", "a sequence of 2^31 tiles is not refused");
+  }
+}
+
 }  // namespace
 
 int main() {
   run_all<uint16_t>();
   run_all<uint32_t>();
+  run_far<uint16_t>();
+  run_far<uint32_t>();
   return finish("ragged index check");
 }

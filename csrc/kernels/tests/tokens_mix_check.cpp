@@ -190,6 +190,50 @@ void check_refusals() {
   if (ddl::tm_parts_ok(cbase, part, 2, 10, 16)) fail(name, "cbase[0] != 0");
 }
 
+// Far case: a table whose cbase and documents pass 2^32 and 2^40 (nothing of that size is materialised): chosen
+// entries through tm_order_at against the definition evaluated here part by part, inner permutations included.
+void check_far(Lcg* rng) {
+  const char* name = "far table";
+  const std::vector<int64_t> n_docs = {(int64_t{1} << 33) + 3, 1000, (int64_t{1} << 40) + 11, 7};
+  const std::vector<int64_t> full = {1, 5000000, 2, 0};
+  const std::vector<int64_t> k = {int64_t{1} << 31, 999, (int64_t{1} << 39) + 1, 7};
+  Mix m = make_mix(name, (int64_t{1} << 32) + 7, n_docs, full, k, 3, true, rng);
+  if (!ddl::tm_parts_ok(m.cbase, m.part, m.parts, m.n_corpus, m.n())) fail(name, "a valid part table is refused");
+  if (m.cbase[1] <= (int64_t{1} << 32) || m.n() <= (int64_t{1} << 41)) fail(name, "the table is not far");
+  const Checked<int64_t> cbase_v{m.cbase, m.parts + 1, name, "cbase read out of range"};
+  const Checked<ddl::MixPart> part_v{m.part, m.parts, name, "part table read out of range"};
+  auto sigma = [&](int p, int64_t r) {
+    if (p < 0 || p >= m.parts || r < 0 || r >= m.extras[p]) {
+      fail(name, "inner permutation asked outside its extra documents");
+      return int64_t{0};
+    }
+    return m.inner[p].at(r);
+  };
+  std::vector<int64_t> entries = {0, (int64_t{1} << 31) - 1, int64_t{1} << 31, (int64_t{1} << 32) - 1, int64_t{1} << 32,
+                                  (int64_t{1} << 32) + 1, int64_t{1} << 40, m.n() - 1, m.n(), -1, INT64_MAX};
+  for (int p = 0; p <= m.parts; ++p)  // both sides of every part border and of every border between passes and extras
+    for (int64_t d : {-1, 0, 1}) {
+      entries.push_back(m.cbase[p] + d);
+      if (p < m.parts) entries.push_back(m.cbase[p] + m.part[p].full_span + d);
+    }
+  for (int c = 0; c < 200; ++c) entries.push_back(((rng->next() << 20) ^ rng->next()) % m.n());
+  for (int64_t v : entries) {
+    ++g_cases;
+    int64_t want = -1;
+    for (int p = 0; p < m.parts && v >= 0; ++p) {
+      if (v >= m.cbase[p + 1]) continue;
+      const int64_t j = v - m.cbase[p];
+      const ddl::MixPart& pt = m.part[p];
+      want = pt.doc_lo + (j < pt.full_span ? j % pt.n_docs : m.inner[p].at(j - pt.full_span));
+      break;
+    }
+    const int64_t got = ddl::tm_order_at([&](int64_t) { return v; }, cbase_v, part_v, m.parts, sigma, 0);
+    if (got != want) fail(name, "entry differs from the definition");
+    if (got != -1 && (got < m.part[0].doc_lo || got >= m.n_corpus)) fail(name, "entry outside the parts");
+  }
+  free_mix(&m);
+}
+
 }  // namespace
 
 int main() {
@@ -225,5 +269,6 @@ int main() {
     check_mix("random", 0, n_docs, full, k, &rng);
   }
   check_refusals();
+  check_far(&rng);
   return finish("tokens mix check");
 }

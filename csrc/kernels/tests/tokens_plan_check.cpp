@@ -141,9 +141,28 @@ void run_all() {
   run_case("long sequences, S = 1", longs, {3, 4}, 1, 5000);
 }
 
+// Far corpus: eight documents of 2^40 tokens among short and empty ones, one of 2^32 + 3, so that the corpus
+// offsets, the table and every seg_src pass 2^32 and 2^40 and reach 2^43. Nothing of that size is materialised.
+std::vector<int64_t> far_lens() {
+  const int64_t big = int64_t{1} << 40;
+  return {5, big, 0, 7, big, big, 1, (int64_t{1} << 32) + 3, big, 0, 0, big, 4097, big, big, 3, big, 11};
+}
+
+// The batch descriptor over the far corpus: src_start and seg_src past 2^43, offsets (the batch's running token
+// count) past 2^41. The rows are long enough that a 2^40-token sequence makes 512 or 3 segments, not 2^37.
+void run_far() {
+  const std::vector<int64_t> lens = far_lens();
+  const std::vector<int64_t> idx = {16, 3, 1, 9, 7, 0, 13, -1, 2, 4, 17, 18, 16, 8};
+  run_case("far, S = 2^31", lens, idx, int64_t{1} << 31, 4096);
+  run_case("far, S = 2^31, capacity exceeded", lens, idx, int64_t{1} << 31, 1000);
+  run_case("far, S = 2^39 + 1", lens, idx, (int64_t{1} << 39) + 1, 64);
+  run_case("far, S = 2^31 - 1", lens, idx, (int64_t{1} << 31) - 1, 4096);
+}
+
 }  // namespace
 
 int main() {
   run_all();
+  run_far();
   return finish("tokens plan check");
 }

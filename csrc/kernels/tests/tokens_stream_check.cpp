@@ -235,9 +235,37 @@ void run_all() {
   run_case("1024 * 1024 + 5 documents", mod_lens(977, 5), stride_order(1024 * 1024 + 5, 31, 7, 977), false);
 }
 
+// Far corpus: eight documents of 2^40 tokens among short and empty ones, one of 2^32 + 3, so that the corpus
+// offsets, the table and every seg_src pass 2^32 and 2^40 and reach 2^43. Nothing of that size is materialised.
+std::vector<int64_t> far_lens() {
+  const int64_t big = int64_t{1} << 40;
+  return {5, big, 0, 7, big, big, 1, (int64_t{1} << 32) + 3, big, 0, 0, big, 4097, big, big, 3, big, 11};
+}
+
+void run_far() {
+  const std::vector<int64_t> lens = far_lens();
+  const std::vector<int64_t> order = {16, 3, 1, 9, 7, 0, 13, 2, 4, 17, 5, 12, 8, 6, 11, 10, 14, 15};
+  ++g_cases;
+  Corpus c = make_corpus("far", lens, order);
+  const int64_t* table = c.table = replay_table("far", c);
+  if (table[c.n] <= (int64_t{1} << 43)) fail("far", "the stream is not far");
+  for (int64_t S : {6, 37, 512}) {
+    for (int64_t rows : {1, 3}) {
+      std::vector<int64_t> bases = {((int64_t{1} << 32) + S - 1) / S, (int64_t{1} << 40) / S, (int64_t{1} << 43) / S - 1};
+      for (int64_t i = 1; i <= c.n; ++i) bases.push_back(table[i] / S - 1);  // the rows across every document border
+      for (int64_t row_base : bases) {
+        run_plan("far", c, table, row_base, rows, S, rows * S + rows);
+        run_plan("far", c, table, row_base, rows, S, 1);
+      }
+    }
+  }
+  free_corpus(&c);
+}
+
 }  // namespace
 
 int main() {
   run_all();
+  run_far();
   return finish("tokens stream check");
 }

@@ -246,9 +246,42 @@ void run_all() {
   free_corpus(&c);
 }
 
+// Far corpus: eight documents of 2^40 tokens among short and empty ones, one of 2^32 + 3, so that the corpus
+// offsets, the table and every seg_src pass 2^32 and 2^40 and reach 2^43. Nothing of that size is materialised.
+std::vector<int64_t> far_lens() {
+  const int64_t big = int64_t{1} << 40;
+  return {5, big, 0, 7, big, big, 1, (int64_t{1} << 32) + 3, big, 0, 0, big, 4097, big, big, 3, big, 11};
+}
+
+void run_far() {
+  const std::vector<int64_t> lens = far_lens();
+  const std::vector<int64_t> order = {16, 3, 1, 9, 7, 0, 13, 2, 4, 17, 5, 12, 8, 6, 11, 10, 14, 15};
+  ++g_cases;
+  Corpus c = make_corpus("far", lens, order);
+  serial_table(&c);
+  const int64_t T = c.table[c.n];
+  if (T <= (int64_t{1} << 43)) fail("far", "the stream is not far");
+  for (int64_t S : {6, 37, 512}) {
+    const int64_t full = T / S;
+    std::vector<int64_t> sel = {0, full - 1, (int64_t{1} << 31) / S, (int64_t{1} << 32) / S, (int64_t{1} << 32) / S + 1,
+                                (int64_t{1} << 40) / S, (int64_t{1} << 43) / S};
+    for (int64_t i = 1; i < c.n; ++i)  // the rows on both sides of, and across, every document border
+      for (int64_t d : {-1, 0, 1}) sel.push_back(c.table[i] / S + d);
+    for (int64_t& r : sel) r = r < 0 ? 0 : (r > full - 1 ? full - 1 : r);
+    const int64_t rows = static_cast<int64_t>(sel.size());
+    run_plan("far", c, sel, S, rows * S);
+    run_plan("far", c, sel, S, rows + 1);
+    std::vector<int64_t> bad = sel;
+    bad[3] = full;  // the first row past the full rows
+    run_plan("far, one invalid", c, bad, S, rows * S);
+  }
+  free_corpus(&c);
+}
+
 }  // namespace
 
 int main() {
   run_all();
+  run_far();
   return finish("tokens stream rows check");
 }

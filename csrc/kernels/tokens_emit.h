@@ -54,6 +54,8 @@ __device__ __forceinline__ TiRow ti_prologue(TokenSpec& sp, uint32_t bx, int32_t
       if (i < sp.n_seg) stage_src(i);
     }
   r.n_cu = ti_cu_entries(sp.n_seg, cu_cap);
+  // cu_seqlens is int32 by its consumers' contract: a batch's own stream stays below 2^31 tokens (the ops refuse
+  // more). A flat stream that starts further into a buffer gets the low 32 bits, which is no contract.
   if (sp.cu_seqlens_out != nullptr && bx == 0)  // owned copy of the sequence starts (cu_seqlens)
     for (int64_t i = threadIdx.x; i <= r.n_cu; i += kTiThreads)
       sp.cu_seqlens_out[i] = static_cast<int32_t>(sp.seg_offsets[i]);

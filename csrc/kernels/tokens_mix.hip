@@ -2,7 +2,7 @@
 // epoch. token_stream_table and the stream plans then run on it as on any explicit index (RowIndex mode 1), so a
 // mixture costs this one kernel and 8 bytes per order entry; all the index arithmetic is tokens_mix.h.
 //
-// One thread per order entry, one 8-byte store per lane, consecutive lanes to consecutive entries. The spec (the
+// One thread per order entry (orders of 2^32 entries or more: a grid-stride loop), one 8-byte store per lane, consecutive lanes to consecutive entries. The spec (the
 // outer RowIndex, the part table, the inner permutations' keys: about 1.6 KB) is the kernel's argument. A lane's
 // part number differs from its neighbour's, and a kernel argument indexed by it would be copied to scratch, so each
 // workgroup first stages the part table into LDS -- part q by lane q, the argument indexed by the loop counter only
@@ -45,8 +45,10 @@ __global__ void __launch_bounds__(kTmThreads) token_mix_order_kernel(MixOrderSpe
   }
   if (t == 0) cbase[sp.parts] = sp.cbase[sp.parts];
   __syncthreads();
-  const int64_t i = static_cast<int64_t>(blockIdx.x) * kTmThreads + t;
-  if (i < sp.n) sp.order[i] = tm_order_at(TmPhi{sp.ri}, cbase, part, sp.parts, TmSigma{keys, sp.inner_shuffle}, i);
+  // grid-stride: a launch holds fewer than 2^32 threads (kTmMaxBlocks), an order may hold more entries
+  const int64_t stride = static_cast<int64_t>(gridDim.x) * kTmThreads;
+  for (int64_t i = static_cast<int64_t>(blockIdx.x) * kTmThreads + t; i < sp.n; i += stride)
+    sp.order[i] = tm_order_at(TmPhi{sp.ri}, cbase, part, sp.parts, TmSigma{keys, sp.inner_shuffle}, i);
 }
 
 bool inner_keys_ok(const FeistelKeys& f, int64_t n_docs) {
@@ -65,8 +67,10 @@ int token_mix_order(const MixOrderSpec& spec, hipStream_t st) {
       if (tm_extras(spec.cbase, spec.part, p) > 0 && !inner_keys_ok(spec.keys[p], spec.part[p].n_docs)) return -2;
     }
   }
-  const int64_t blocks = tm_blocks(spec.n);
-  if (blocks > 0x7FFFFFFF) return -4;
+  // One thread per entry up to kTmMaxBlocks workgroups; past that the lanes stride. A grid of 2^32 threads or more
+  // ran only its count modulo 2^32: an order of 2^32 + k entries had just its first k written.
+  constexpr int64_t kTmMaxBlocks = (int64_t{1} << 32) / kTmThreads - 1;
+  const int64_t blocks = tm_blocks(spec.n) < kTmMaxBlocks ? tm_blocks(spec.n) : kTmMaxBlocks;
   hipLaunchKernelGGL(token_mix_order_kernel, dim3(static_cast<uint32_t>(blocks)), dim3(kTmThreads), 0, st, spec);
   return static_cast<int>(hipGetLastError());
 }

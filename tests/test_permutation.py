@@ -5,34 +5,8 @@ import pytest
 from hypothesis import given, settings
 from hypothesis import strategies as st
 
-from ddl_amd.permutation import EpochOrder, FeistelPermutation, half_bits_for, round_keys
-
-MASK = (1 << 64) - 1
-
-
-def _mix(z):
-    z &= MASK
-    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & MASK
-    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & MASK
-    return z ^ (z >> 31)
-
-
-def _py_perm(i, n, seed, epoch):
-    """Independent scalar reference of csrc/kernels/common.h::feistel_perm."""
-    keys = round_keys(seed, epoch)
-    h = half_bits_for(n)
-    mask = (1 << h) - 1
-
-    def once(x):
-        left, right = x >> h, x & mask
-        for k in keys:
-            left, right = right, left ^ (_mix(right ^ k) & mask)
-        return (left << h) | right
-
-    x = once(i)
-    while x >= n:
-        x = once(x)
-    return x
+from ddl_amd.permutation import EpochOrder, FeistelPermutation
+from tests.feistel_ref import py_perm as _py_perm  # the independent scalar reference, shared with the GPU suites
 
 
 @pytest.mark.parametrize("n", [1, 2, 3, 4, 5, 7, 8, 15, 16, 17, 1000, 4095, 4096, 4097, 100_520])
