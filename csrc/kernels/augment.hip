@@ -24,13 +24,12 @@
 // the same kernel with the taps read from global memory.
 #include <algorithm>
 
-#include "common.h"
+#include "elem.h"
 #include "launch.h"
 
 namespace ddl {
 namespace {
 
-constexpr int kThreads = 256;
 constexpr int kBandMaxRows = 16;
 constexpr int64_t kBandLdsBudget = 32 * 1024;  // 4-5 workgroups (16-20 waves) per CU
 static_assert(sizeof(CropBox) == 5 * sizeof(int32_t), "CropBox must match the [B, 5] int32 boxes tensor");
@@ -78,14 +77,6 @@ __device__ CropBox draw_crop(const AugmentSpec& a, uint64_t sample) {
   return b;
 }
 
-template <typename T>
-__device__ __forceinline__ float ld(const T* p) {
-  if constexpr (sizeof(T) == 2)
-    return bf16_bits_to_f32(*reinterpret_cast<const uint16_t*>(p));
-  else
-    return static_cast<float>(*p);
-}
-
 // One thread per image: draw its crop box (10 attempts of hash + log/exp/sqrt)
 // once, instead of once per workgroup of the resampling kernel.
 __global__ void __launch_bounds__(kThreads) rrc_boxes_kernel(AugmentSpec a, int64_t batch, RowIndex ri,
@@ -121,8 +112,8 @@ __device__ __forceinline__ float src_coord(int o, float f) {
 // pixel (y, x) of channel c.
 constexpr int kPx = 4;
 
-template <int OUT_BF16, typename Tap>
-__device__ __forceinline__ void resample_band(void* __restrict__ dst, int64_t img, const AugmentSpec& a,
+template <typename Tout, typename Tap>
+__device__ __forceinline__ void resample_band(Tout* __restrict__ dst, int64_t img, const AugmentSpec& a,
                                               const CropBox& b, int oy0, int oy1, const Affine& aff, Tap tap) {
   const int ow = a.out_w, C = a.channels;
   const int64_t opix = static_cast<int64_t>(a.out_h) * ow;
@@ -162,20 +153,10 @@ __device__ __forceinline__ void resample_band(void* __restrict__ dst, int64_t im
         if (aff.enabled) v[k] = fmaf(v[k], aff.scale[c], aff.bias[c]);
       }
       const int64_t oc = o + static_cast<int64_t>(c) * opix;
-      if constexpr (OUT_BF16) {
-        uint16_t* d = static_cast<uint16_t*>(dst) + oc;
-        if (vec) {
-          *reinterpret_cast<uint2*>(d) = make_uint2(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]));
-        } else {
-          for (int k = 0; k < kPx && q0 + k < n; ++k) d[k] = f32_to_bf16_bits(v[k]);
-        }
+      if (vec) {
+        Elem<Tout>::template store<kPx>(dst + oc, v);
       } else {
-        float* d = static_cast<float*>(dst) + oc;
-        if (vec) {
-          *reinterpret_cast<float4*>(d) = make_float4(v[0], v[1], v[2], v[3]);
-        } else {
-          for (int k = 0; k < kPx && q0 + k < n; ++k) d[k] = v[k];
-        }
+        for (int k = 0; k < kPx && q0 + k < n; ++k) Elem<Tout>::store1(dst + oc + k, v[k]);
       }
     }
   }
@@ -199,15 +180,14 @@ __device__ __forceinline__ void resample_band(void* __restrict__ dst, int64_t im
 // resample_band: bit-identical output.
 constexpr int kCpl = 2;        // adjacent output columns per lane
 constexpr int kColGroups = 2;  // groups of 64 * kCpl columns held in registers: out_w <= 256 per pass
-static_assert(kCpl == 2 || kCpl == 4, "the vector stores below pack 2 or 4 values");
 
-template <int OUT_BF16, typename Tin, int HWC, int NC>
-__device__ __forceinline__ void resample_band_cols(void* __restrict__ dst, int64_t img, const AugmentSpec& a,
+template <typename Tout, typename Tin, int HWC, int NC>
+__device__ __forceinline__ void resample_band_cols(Tout* __restrict__ dst, int64_t img, const AugmentSpec& a,
                                                    const CropBox& b, int oy0, int oy1, const Affine& aff,
                                                    const uint8_t* __restrict__ lds, uint32_t head, uint32_t stride,
                                                    uint32_t nrows, int ylo) {
   constexpr uint32_t kSz = static_cast<uint32_t>(sizeof(Tin));
-  constexpr bool kEdgeByWeight = sizeof(Tin) == 1;  // garbage taps are finite only for uint8
+  constexpr bool kEdgeByWeight = std::is_same_v<Tin, uint8_t>;  // garbage taps are finite only for uint8
   constexpr int kWaves = kThreads / 64;
   constexpr int kGw = 64 * kCpl;  // columns per group
   constexpr int kC = NC > 0 ? NC : kMaxAffineChannels;
@@ -262,10 +242,10 @@ __device__ __forceinline__ void resample_band_cols(void* __restrict__ dst, int64
           const uint8_t* lb = lds + (static_cast<uint32_t>(c) * cstep + rb);
 #pragma unroll
           for (int j = 0; j < kCpl; ++j) {
-            const float v00 = ld(reinterpret_cast<const Tin*>(la + xa[g][j]));
-            const float v01 = ld(reinterpret_cast<const Tin*>(la + xb[g][j]));
-            const float v10 = ld(reinterpret_cast<const Tin*>(lb + xa[g][j]));
-            const float v11 = ld(reinterpret_cast<const Tin*>(lb + xb[g][j]));
+            const float v00 = Elem<Tin>::load1(reinterpret_cast<const Tin*>(la + xa[g][j]));
+            const float v01 = Elem<Tin>::load1(reinterpret_cast<const Tin*>(la + xb[g][j]));
+            const float v10 = Elem<Tin>::load1(reinterpret_cast<const Tin*>(lb + xa[g][j]));
+            const float v11 = Elem<Tin>::load1(reinterpret_cast<const Tin*>(lb + xb[g][j]));
             const float top = v00 + (v01 - v00) * wx[g][j];
             const float bot = v10 + (v11 - v10) * wx[g][j];
             v[c][j] = top + (bot - top) * wy;
@@ -281,26 +261,12 @@ __device__ __forceinline__ void resample_band_cols(void* __restrict__ dst, int64
                                  : (aff.enabled ? fmaf(v[c][j], aff.scale[c], aff.bias[c]) : v[c][j]);
           const int64_t oc = o + static_cast<int64_t>(c) * opix;
           if (pair_stores && col + kCpl <= ow) {
-            if constexpr (OUT_BF16) {
-              if constexpr (kCpl == 2)
-                *reinterpret_cast<uint32_t*>(static_cast<uint16_t*>(dst) + oc) = pack_bf16x2(y[0], y[1]);
-              else
-                *reinterpret_cast<uint2*>(static_cast<uint16_t*>(dst) + oc) =
-                    make_uint2(pack_bf16x2(y[0], y[1]), pack_bf16x2(y[2], y[3]));
-            } else {
-              if constexpr (kCpl == 2)
-                *reinterpret_cast<float2*>(static_cast<float*>(dst) + oc) = make_float2(y[0], y[1]);
-              else
-                *reinterpret_cast<float4*>(static_cast<float*>(dst) + oc) = make_float4(y[0], y[1], y[2], y[3]);
-            }
+            Elem<Tout>::template store<kCpl>(dst + oc, y);
           } else {
 #pragma unroll
             for (int j = 0; j < kCpl; ++j) {
               if (col + j >= ow) break;
-              if constexpr (OUT_BF16)
-                static_cast<uint16_t*>(dst)[oc + j] = f32_to_bf16_bits(y[j]);
-              else
-                static_cast<float*>(dst)[oc + j] = y[j];
+              Elem<Tout>::store1(dst + (oc + j), y[j]);
             }
           }
         }
@@ -313,8 +279,8 @@ __device__ __forceinline__ void resample_band_cols(void* __restrict__ dst, int64
 // LDS layout: (plane p, band row r) rows of `stride` bytes; row (p, r) holds
 // the 16 B-aligned global chunks covering the crop's span of that source row,
 // which therefore starts head(p, r) = (global address & 15) bytes into it.
-template <typename Tin, int HWC, int OUT_BF16>
-__global__ void __launch_bounds__(kThreads) rrc_band_kernel(void* __restrict__ dst, const Tin* __restrict__ src,
+template <typename Tin, int HWC, typename Tout>
+__global__ void __launch_bounds__(kThreads) rrc_band_kernel(Tout* __restrict__ dst, const Tin* __restrict__ src,
                                                            AugmentSpec a, int32_t bands, int32_t band_rows,
                                                            int32_t lds_cap, RowIndex ri, Affine aff,
                                                            const CropBox* __restrict__ boxes) {
@@ -340,9 +306,9 @@ __global__ void __launch_bounds__(kThreads) rrc_band_kernel(void* __restrict__ d
   const uint32_t stride = cpr << 4;
 
   if (static_cast<int64_t>(planes) * nrows * stride > lds_cap) {  // taps from global memory
-    resample_band<OUT_BF16>(dst, img, a, b, oy0, oy1, aff, [&](int c, int y, int x) {
+    resample_band(dst, img, a, b, oy0, oy1, aff, [&](int c, int y, int x) {
       const int p = HWC ? 0 : c, ci = HWC ? c : 0;
-      return ld(s + p * plane_elems + (b.y + y) * row_pitch + static_cast<int64_t>(b.x + x) * cin + ci);
+      return Elem<Tin>::load1(s + p * plane_elems + (b.y + y) * row_pitch + static_cast<int64_t>(b.x + x) * cin + ci);
     });
     return;
   }
@@ -394,18 +360,18 @@ __global__ void __launch_bounds__(kThreads) rrc_band_kernel(void* __restrict__ d
   if ((pitch_lo & 15u) == 0 && (planes == 1 || (plane_lo & 15u) == 0)) {
     // every LDS row starts `base_lo & 15` bytes into its first chunk (kernel-uniform branch)
     if (a.channels == 3)
-      resample_band_cols<OUT_BF16, Tin, HWC, 3>(dst, img, a, b, oy0, oy1, aff, lds, base_lo & 15u, stride, nrows, ylo);
+      resample_band_cols<Tout, Tin, HWC, 3>(dst, img, a, b, oy0, oy1, aff, lds, base_lo & 15u, stride, nrows, ylo);
     else
-      resample_band_cols<OUT_BF16, Tin, HWC, 0>(dst, img, a, b, oy0, oy1, aff, lds, base_lo & 15u, stride, nrows, ylo);
+      resample_band_cols<Tout, Tin, HWC, 0>(dst, img, a, b, oy0, oy1, aff, lds, base_lo & 15u, stride, nrows, ylo);
     return;
   }
-  resample_band<OUT_BF16>(dst, img, a, b, oy0, oy1, aff, [&](int c, int y, int x) {
+  resample_band(dst, img, a, b, oy0, oy1, aff, [&](int c, int y, int x) {
     const uint32_t p = HWC ? 0u : static_cast<uint32_t>(c);
     const uint32_t ci = HWC ? static_cast<uint32_t>(c) : 0u;
     const uint32_t r = static_cast<uint32_t>(y - ylo);
     const uint32_t head = (base_lo + p * plane_lo + r * pitch_lo) & 15u;
     const uint32_t off = (p * nrows + r) * stride + head + (static_cast<uint32_t>(x) * cin + ci) * kSz;
-    return ld(reinterpret_cast<const Tin*>(lds + off));
+    return Elem<Tin>::load1(reinterpret_cast<const Tin*>(lds + off));
   });
 }
 
@@ -429,28 +395,20 @@ BandPlan plan_band(const AugmentSpec& a, int hwc, int elem, int path) {
   return {kBandMaxRows, 0};
 }
 
-template <typename Tin, int HWC>
-int launch_rrc(void* dst, int32_t out_dt, const void* src, int64_t batch, const AugmentSpec& a, const RowIndex& ri,
+template <typename Tin, typename Tout>
+int launch_rrc(void* dst, const void* src, int64_t batch, const AugmentSpec& a, int hwc, const RowIndex& ri,
                const Affine& aff, int32_t* boxes_out, int path, hipStream_t st) {
-  const BandPlan pl = plan_band(a, HWC, static_cast<int>(sizeof(Tin)), path);
+  const BandPlan pl = plan_band(a, hwc, static_cast<int>(sizeof(Tin)), path);
   if (path == 1 && pl.lds == 0) return -5;  // LDS path requested but the geometry does not fit the budget
   const int64_t bands = (a.out_h + pl.rows - 1) / pl.rows;
   if (batch * bands >= (int64_t{1} << 31)) return -4;
   auto* boxes = reinterpret_cast<CropBox*>(boxes_out);
   hipLaunchKernelGGL(rrc_boxes_kernel, dim3(static_cast<uint32_t>((batch + kThreads - 1) / kThreads)), dim3(kThreads),
                      0, st, a, batch, ri, boxes);
-  const dim3 grid(static_cast<uint32_t>(batch * bands));
-  const auto* s = static_cast<const Tin*>(src);
-  const size_t lds = static_cast<size_t>(pl.lds);
-  const int32_t nb = static_cast<int32_t>(bands), cap = static_cast<int32_t>(pl.lds);
-  if (out_dt == kBF16)
-    hipLaunchKernelGGL((rrc_band_kernel<Tin, HWC, 1>), grid, dim3(kThreads), lds, st, dst, s, a, nb, pl.rows, cap, ri,
-                       aff, boxes);
-  else if (out_dt == kF32)
-    hipLaunchKernelGGL((rrc_band_kernel<Tin, HWC, 0>), grid, dim3(kThreads), lds, st, dst, s, a, nb, pl.rows, cap, ri,
-                       aff, boxes);
-  else
-    return -1;
+  auto kernel = hwc ? rrc_band_kernel<Tin, 1, Tout> : rrc_band_kernel<Tin, 0, Tout>;
+  hipLaunchKernelGGL(kernel, dim3(static_cast<uint32_t>(batch * bands)), dim3(kThreads), static_cast<size_t>(pl.lds),
+                     st, static_cast<Tout*>(dst), static_cast<const Tin*>(src), a, static_cast<int32_t>(bands), pl.rows,
+                     static_cast<int32_t>(pl.lds), ri, aff, boxes);
   return static_cast<int>(hipGetLastError());
 }
 
@@ -460,23 +418,17 @@ int random_resized_crop(void* dst, int32_t out_dt, const void* src, int32_t in_d
                         const AugmentSpec& a, int hwc, const RowIndex& ri, const Affine& aff, int32_t* boxes_out,
                         int path, hipStream_t st) {
   if (batch <= 0) return 0;
+  if (!row_index_ok(ri, batch)) return -2;
   if (boxes_out == nullptr) return -3;  // [batch, 5] int32 device buffer: boxes are drawn there first
   if (a.channels < 1 || a.channels > kMaxAffineChannels || a.in_h < 1 || a.in_w < 1 || a.out_h < 1 || a.out_w < 1 ||
       a.out_w > 8192)  // FastDiv range: (band pixel index) * out_w < 2^32
     return -2;
   if (path < 0 || path > 2) return -2;
-  switch (in_dt) {
-    case kU8:
-      return hwc ? launch_rrc<uint8_t, 1>(dst, out_dt, src, batch, a, ri, aff, boxes_out, path, st)
-                 : launch_rrc<uint8_t, 0>(dst, out_dt, src, batch, a, ri, aff, boxes_out, path, st);
-    case kF32:
-      return hwc ? launch_rrc<float, 1>(dst, out_dt, src, batch, a, ri, aff, boxes_out, path, st)
-                 : launch_rrc<float, 0>(dst, out_dt, src, batch, a, ri, aff, boxes_out, path, st);
-    case kBF16:
-      return hwc ? launch_rrc<uint16_t, 1>(dst, out_dt, src, batch, a, ri, aff, boxes_out, path, st)
-                 : launch_rrc<uint16_t, 0>(dst, out_dt, src, batch, a, ri, aff, boxes_out, path, st);
-  }
-  return -1;
+  return with_dtype<kU8, kF32, kBF16>(in_dt, [&](auto in) {
+    return with_dtype<kBF16, kF32>(out_dt, [&](auto out) {
+      return launch_rrc<decltype(in), decltype(out)>(dst, src, batch, a, hwc, ri, aff, boxes_out, path, st);
+    });
+  });
 }
 
 }  // namespace ddl

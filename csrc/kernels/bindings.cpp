@@ -78,7 +78,6 @@ ddl::RowIndex make_index(int mode, uintptr_t idx, int64_t base, const std::vecto
   ri.mode = mode;
   ri.idx = as_ptr<const int64_t>(idx);
   ri.base = base;
-  if (mode == 1 && !idx) throw std::invalid_argument("index mode 1 needs an index vector");
   if (mode == 2) ri.keys = make_keys(keys, n, half_bits);
   return ri;
 }

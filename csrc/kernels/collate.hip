@@ -11,66 +11,25 @@
 // one [B, nValues] row block (ddl/mpi_dataloader.py:193-196). For device
 // batches we emit the column groups as contiguous tensors in one pass fused
 // with the permutation gather and the dtype cast.
-#include "common.h"
+#include "elem.h"
 #include "launch.h"
 
 namespace ddl {
 namespace {
 
-constexpr int kThreads = 256;
 constexpr int kPix = 2048;  // pixels per tile: 8 per lane
 // Dynamic LDS a launch may ask for without raising the kernel's limit through a function attribute.
 constexpr size_t kPlainLdsBytes = 64 * 1024;
 
-template <typename T>
-struct Px;
-template <>
-struct Px<uint8_t> {
-  static __device__ __forceinline__ float get(const uint8_t* s, int i) { return static_cast<float>(s[i]); }
-};
-template <>
-struct Px<float> {
-  static __device__ __forceinline__ float get(const float* s, int i) { return s[i]; }
-};
-template <>
-struct Px<uint16_t> {  // bf16 bits
-  static __device__ __forceinline__ float get(const uint16_t* s, int i) { return bf16_bits_to_f32(s[i]); }
-};
-
-template <int OUT_BF16>
-struct Out8 {
-  static __device__ __forceinline__ void store(void* dst, int64_t off, const float (&f)[8]) {
-    if constexpr (OUT_BF16) {
-      uint4 v;
-      v.x = pack_bf16x2(f[0], f[1]);
-      v.y = pack_bf16x2(f[2], f[3]);
-      v.z = pack_bf16x2(f[4], f[5]);
-      v.w = pack_bf16x2(f[6], f[7]);
-      *reinterpret_cast<uint4*>(static_cast<uint16_t*>(dst) + off) = v;
-    } else {
-      float* d = static_cast<float*>(dst) + off;
-      *reinterpret_cast<float4*>(d) = make_float4(f[0], f[1], f[2], f[3]);
-      *reinterpret_cast<float4*>(d + 4) = make_float4(f[4], f[5], f[6], f[7]);
-    }
-  }
-  static __device__ __forceinline__ void store1(void* dst, int64_t off, float f) {
-    if constexpr (OUT_BF16)
-      static_cast<uint16_t*>(dst)[off] = f32_to_bf16_bits(f);
-    else
-      static_cast<float*>(dst)[off] = f;
-  }
-};
-
 // grid: (tiles_per_image * batch); LDS: tile_px * C * sizeof(Tin) bytes. tile_px is kPix, or a smaller
 // multiple of 8 for wide pixels (launch_hwc); lanes past the tile's pixels only help to stage it.
-template <typename Tin, int OUT_BF16>
-__global__ void __launch_bounds__(kThreads) hwc_to_chw_kernel(void* __restrict__ dst, const Tin* __restrict__ src,
+template <typename Tin, typename Tout>
+__global__ void __launch_bounds__(kThreads) hwc_to_chw_kernel(Tout* __restrict__ dst, const Tin* __restrict__ src,
                                                               int64_t pixels, int32_t channels, int64_t tiles,
                                                               int32_t tile_px, RowIndex ri, Affine aff) {
   extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
   Tin* tile = reinterpret_cast<Tin*>(lds_raw);
-  const int64_t img = blockIdx.x / static_cast<uint32_t>(tiles);  // 32-bit: grid < 2^32 blocks
-  const int64_t t = blockIdx.x - static_cast<uint32_t>(img) * static_cast<uint32_t>(tiles);
+  const auto [img, t] = row_chunk(blockIdx.x, tiles);  // grid < 2^32 blocks
   const int64_t p0 = t * tile_px;
   const int npx = static_cast<int>(pixels - p0 < tile_px ? pixels - p0 : tile_px);
   const int64_t srow = source_row(ri, img);
@@ -95,11 +54,11 @@ __global__ void __launch_bounds__(kThreads) hwc_to_chw_kernel(void* __restrict__
     if (px + 8 <= npx && ((obase + px) & 7) == 0) {
       float f[8];
 #pragma unroll
-      for (int k = 0; k < 8; ++k) f[k] = fmaf(Px<Tin>::get(tile, (px + k) * channels + c), sc, bi);
-      Out8<OUT_BF16>::store(dst, obase + px, f);
+      for (int k = 0; k < 8; ++k) f[k] = fmaf(Elem<Tin>::load1(tile + ((px + k) * channels + c)), sc, bi);
+      Elem<Tout>::template store<8>(dst + (obase + px), f);
     } else {
       for (int k = 0; k < 8 && px + k < npx; ++k)
-        Out8<OUT_BF16>::store1(dst, obase + px + k, fmaf(Px<Tin>::get(tile, (px + k) * channels + c), sc, bi));
+        Elem<Tout>::store1(dst + (obase + px + k), fmaf(Elem<Tin>::load1(tile + ((px + k) * channels + c)), sc, bi));
     }
   }
 }
@@ -114,13 +73,12 @@ __global__ void __launch_bounds__(kThreads) hwc_to_chw_kernel(void* __restrict__
 // de-interleaves in registers.
 constexpr int kPix3 = 4096;
 
-template <int OUT_BF16>
-__global__ void __launch_bounds__(kThreads) hwc3_u8_to_chw_kernel(void* __restrict__ dst, const uint8_t* __restrict__ src,
+template <typename Tout>
+__global__ void __launch_bounds__(kThreads) hwc3_u8_to_chw_kernel(Tout* __restrict__ dst, const uint8_t* __restrict__ src,
                                                                   int64_t pixels, int64_t tiles, RowIndex ri,
                                                                   Affine aff) {
   __shared__ __attribute__((aligned(16))) uint8_t tile[kPix3 * 3];
-  const int64_t img = blockIdx.x / static_cast<uint32_t>(tiles);  // 32-bit: grid < 2^32 blocks
-  const int64_t t = blockIdx.x - static_cast<uint32_t>(img) * static_cast<uint32_t>(tiles);
+  const auto [img, t] = row_chunk(blockIdx.x, tiles);  // grid < 2^32 blocks
   const int64_t p0 = t * kPix3;
   const int npx = static_cast<int>(pixels - p0 < kPix3 ? pixels - p0 : kPix3);
   const uint8_t* s = src + (source_row(ri, img) * pixels + p0) * 3;
@@ -161,9 +119,9 @@ __global__ void __launch_bounds__(kThreads) hwc3_u8_to_chw_kernel(void* __restri
         }
         const int64_t o = out_img + c * pixels + p0 + px;
         if ((o & 7) == 0) {
-          Out8<OUT_BF16>::store(dst, o, f);
+          Elem<Tout>::template store<8>(dst + o, f);
         } else {
-          for (int k = 0; k < 8; ++k) Out8<OUT_BF16>::store1(dst, o + k, f[k]);
+          for (int k = 0; k < 8; ++k) Elem<Tout>::store1(dst + (o + k), f[k]);
         }
       }
     } else if (px < npx) {
@@ -171,8 +129,8 @@ __global__ void __launch_bounds__(kThreads) hwc3_u8_to_chw_kernel(void* __restri
         const float sc = aff.enabled ? aff.scale[c] : 1.f;
         const float bi = aff.enabled ? aff.bias[c] : 0.f;
         for (int k = 0; k < 8 && px + k < npx; ++k)
-          Out8<OUT_BF16>::store1(dst, out_img + c * pixels + p0 + px + k,
-                                 fmaf(static_cast<float>(tile[(px + k) * 3 + c]), sc, bi));
+          Elem<Tout>::store1(dst + (out_img + c * pixels + p0 + px + k),
+                             fmaf(static_cast<float>(tile[(px + k) * 3 + c]), sc, bi));
       }
     }
   }
@@ -188,24 +146,18 @@ size_t hwc_lds_limit() {
   return static_cast<size_t>(per_block) < kPlainLdsBytes ? static_cast<size_t>(per_block) : kPlainLdsBytes;
 }
 
-template <typename Tin>
-int launch_hwc(void* dst, int32_t out_dt, const void* src, int64_t batch, int64_t pixels, int32_t channels,
-               const RowIndex& ri, const Affine& aff, hipStream_t st) {
-  if constexpr (sizeof(Tin) == 1) {
-    if (channels == 3 && (out_dt == kBF16 || out_dt == kF32)) {
+template <typename Tin, typename Tout>
+int launch_hwc(void* dst, const void* src, int64_t batch, int64_t pixels, int32_t channels, const RowIndex& ri,
+               const Affine& aff, hipStream_t st) {
+  if constexpr (std::is_same_v<Tin, uint8_t>) {
+    if (channels == 3) {
       const int64_t tiles3 = (pixels + kPix3 - 1) / kPix3;
       if (batch * tiles3 >= (int64_t{1} << 32)) return -4;  // as below: one block per (image, tile)
-      const dim3 grid3(static_cast<uint32_t>(batch * tiles3));
-      if (out_dt == kBF16)
-        hipLaunchKernelGGL(hwc3_u8_to_chw_kernel<1>, grid3, dim3(kThreads), 0, st, dst,
-                           static_cast<const uint8_t*>(src), pixels, tiles3, ri, aff);
-      else
-        hipLaunchKernelGGL(hwc3_u8_to_chw_kernel<0>, grid3, dim3(kThreads), 0, st, dst,
-                           static_cast<const uint8_t*>(src), pixels, tiles3, ri, aff);
+      hipLaunchKernelGGL(hwc3_u8_to_chw_kernel<Tout>, dim3(static_cast<uint32_t>(batch * tiles3)), dim3(kThreads), 0,
+                         st, static_cast<Tout*>(dst), static_cast<const uint8_t*>(src), pixels, tiles3, ri, aff);
       return static_cast<int>(hipGetLastError());
     }
   }
-  if (out_dt != kBF16 && out_dt != kF32) return -1;
   // The tile is kPix pixels while that fits the LDS a workgroup may have (u8 and bf16 at every channel count,
   // f32 up to 8 channels); wider pixels halve it (f32 x 16 channels: 512 pixels), so the request never
   // passes the limit and no shape fails at launch.
@@ -217,13 +169,9 @@ int launch_hwc(void* dst, int32_t out_dt, const void* src, int64_t batch, int64_
   const size_t lds = tile_px * px_bytes;
   const int64_t tiles = (pixels + tile_px - 1) / tile_px;
   if (batch * tiles >= (int64_t{1} << 32)) return -4;  // the grid is one block per (image, tile)
-  const dim3 grid(static_cast<uint32_t>(batch * tiles));
-  if (out_dt == kBF16)
-    hipLaunchKernelGGL((hwc_to_chw_kernel<Tin, 1>), grid, dim3(kThreads), lds, st, dst, static_cast<const Tin*>(src),
-                       pixels, channels, tiles, tile_px, ri, aff);
-  else
-    hipLaunchKernelGGL((hwc_to_chw_kernel<Tin, 0>), grid, dim3(kThreads), lds, st, dst, static_cast<const Tin*>(src),
-                       pixels, channels, tiles, tile_px, ri, aff);
+  hipLaunchKernelGGL((hwc_to_chw_kernel<Tin, Tout>), dim3(static_cast<uint32_t>(batch * tiles)), dim3(kThreads), lds,
+                     st, static_cast<Tout*>(dst), static_cast<const Tin*>(src), pixels, channels, tiles, tile_px, ri,
+                     aff);
   return static_cast<int>(hipGetLastError());
 }
 
@@ -321,27 +269,32 @@ __device__ __forceinline__ T* split_out(const SplitSpec& spec, int g, int64_t ro
          (row - slot * spec.slot_rows) * spec.width[g] + col;
 }
 
-template <typename Tin, int OUT>
+// One element, src -> dst. Equal dtypes are copied raw, as unsigned integers of their size (any 1/2/4/8-byte dtype,
+// no rounding): Tout is then Tin, and integral; every other pair converts through float.
+template <typename Tout, typename Tin>
+__device__ __forceinline__ auto load_for(const Tin* s) {
+  static_assert(!std::is_integral_v<Tout> || std::is_same_v<Tin, Tout>, "an integral output is a raw copy");
+  if constexpr (std::is_integral_v<Tout>)
+    return *s;
+  else
+    return Elem<Tin>::load1(s);
+}
+template <typename Tout, typename V>
+__device__ __forceinline__ void store_as(Tout* d, V v) {
+  static_assert(!std::is_integral_v<Tout> || std::is_same_v<V, Tout>, "an integral output is a raw copy");
+  if constexpr (std::is_integral_v<Tout>)
+    *d = v;
+  else
+    Elem<Tout>::store1(d, v);
+}
+
+template <typename Tin, typename Tout>
 __global__ void __launch_bounds__(kThreads) split_columns_kernel(SplitSpec spec, const Tin* __restrict__ src,
                                                                  int64_t n_rows, int64_t n_values, RowIndex ri) {
   for_rows(n_rows, n_values, ri, [&](int64_t row, int col, int64_t src_row) {
-    const float v = Px<Tin>::get(src + src_row * n_values, col);
+    const auto v = load_for<Tout>(src + (src_row * n_values + col));
     const int g = group_of(spec, &col);
-    if constexpr (OUT == kBF16)
-      *split_out<uint16_t>(spec, g, row, col, n_rows) = f32_to_bf16_bits(v);
-    else
-      *split_out<float>(spec, g, row, col, n_rows) = v;
-  });
-}
-
-// Same-dtype split: raw element copies (any 1/2/4/8-byte dtype, no rounding).
-template <typename T>
-__global__ void __launch_bounds__(kThreads) split_columns_raw_kernel(SplitSpec spec, const T* __restrict__ src,
-                                                                     int64_t n_rows, int64_t n_values, RowIndex ri) {
-  for_rows(n_rows, n_values, ri, [&](int64_t row, int col, int64_t src_row) {
-    const T v = src[src_row * n_values + col];
-    const int g = group_of(spec, &col);
-    *split_out<T>(spec, g, row, col, n_rows) = v;
+    store_as(split_out<Tout>(spec, g, row, col, n_rows), v);
   });
 }
 
@@ -350,111 +303,76 @@ __global__ void __launch_bounds__(kThreads) split_columns_raw_kernel(SplitSpec s
 // row r taking source row source_row(ri, r) of every group (gather + concat +
 // cast in one pass), in the same 64-row wave tiles: the output write is
 // lane-contiguous, each group's reads are contiguous runs of w_g.
-template <typename Tin, int OUT>
-__global__ void __launch_bounds__(kThreads) pack_columns_kernel(SplitSpec spec, void* __restrict__ dst,
+template <typename Tin, typename Tout>
+__global__ void __launch_bounds__(kThreads) pack_columns_kernel(SplitSpec spec, Tout* __restrict__ dst,
                                                                 int64_t n_rows, int64_t n_values, RowIndex ri) {
   for_rows(n_rows, n_values, ri, [&](int64_t row, int col, int64_t src_row) {
-    const int64_t e = row * n_values + col;
+    Tout* d = dst + (row * n_values + col);
     const int g = group_of(spec, &col);
-    const Tin* s = static_cast<const Tin*>(spec.dst[g]) + src_row * spec.width[g];
-    if constexpr (OUT == kBF16)
-      static_cast<uint16_t*>(dst)[e] = f32_to_bf16_bits(Px<Tin>::get(s, col));
-    else if constexpr (OUT == kF32)
-      static_cast<float*>(dst)[e] = Px<Tin>::get(s, col);
-    else
-      static_cast<Tin*>(dst)[e] = s[col];  // raw (same dtype)
+    store_as(d, load_for<Tout>(static_cast<const Tin*>(spec.dst[g]) + src_row * spec.width[g] + col));
   });
 }
 
-constexpr int kRaw = -1;
+// What split_columns and pack_columns share: the argument checks, the grid of the row walk, and the (Tin, Tout) of
+// the launch -- u8 / f32 / bf16 -> bf16 / f32, or for equal dtypes the unsigned integer of their size, twice.
+template <typename F>
+int launch_columns(const SplitSpec& spec, int32_t in_dt, int64_t n_rows, int64_t n_values, const RowIndex& ri,
+                   F&& launch) {
+  if (n_rows <= 0) return 0;
+  if (!row_index_ok(ri, n_rows)) return -2;
+  if (spec.n_groups < 1 || spec.n_groups > 8) return -2;
+  if (n_values < 1 || n_values > (1 << 24)) return -2;  // 64 rows x n_values fits the tile's 32-bit walk
+  int64_t blocks = (row_walk_waves(n_rows, n_values) + kThreads / 64 - 1) / (kThreads / 64);
+  if (blocks > 8192) blocks = 8192;
+  const dim3 grid(static_cast<uint32_t>(blocks));
+  auto go = [&](auto in, auto out) {
+    launch(grid, in, out);
+    return static_cast<int>(hipGetLastError());
+  };
+  if (spec.out_dt == in_dt) {
+    switch (dtype_size(in_dt)) {
+      case 1: return go(uint8_t{}, uint8_t{});
+      case 2: return go(uint16_t{}, uint16_t{});
+      case 4: return go(uint32_t{}, uint32_t{});
+      case 8: return go(uint64_t{}, uint64_t{});
+    }
+    return -1;
+  }
+  return with_dtype<kF32, kBF16, kU8>(in_dt, [&](auto in) {
+    return with_dtype<kBF16, kF32>(spec.out_dt, [&](auto out) { return go(in, out); });
+  });
+}
 
 }  // namespace
 
 int collate_hwc_to_chw(void* dst, int32_t out_dt, const void* src, int32_t in_dt, int64_t batch, int64_t pixels,
                        int32_t channels, const RowIndex& ri, const Affine& aff, hipStream_t st) {
   if (batch <= 0 || pixels <= 0) return 0;
+  if (!row_index_ok(ri, batch)) return -2;
   if (channels <= 0 || channels > kMaxAffineChannels) return -2;
-  switch (in_dt) {
-    case kU8: return launch_hwc<uint8_t>(dst, out_dt, src, batch, pixels, channels, ri, aff, st);
-    case kF32: return launch_hwc<float>(dst, out_dt, src, batch, pixels, channels, ri, aff, st);
-    case kBF16: return launch_hwc<uint16_t>(dst, out_dt, src, batch, pixels, channels, ri, aff, st);
-  }
-  return -1;
+  return with_dtype<kU8, kF32, kBF16>(in_dt, [&](auto in) {
+    return with_dtype<kBF16, kF32>(out_dt, [&](auto out) {
+      return launch_hwc<decltype(in), decltype(out)>(dst, src, batch, pixels, channels, ri, aff, st);
+    });
+  });
 }
 
 int split_columns(const SplitSpec& spec, const void* src, int32_t in_dt, int64_t n_rows, int64_t n_values,
                   const RowIndex& ri, hipStream_t st) {
-  if (n_rows <= 0) return 0;
-  if (spec.n_groups < 1 || spec.n_groups > 8) return -2;
-  if (n_values < 1 || n_values > (1 << 24)) return -2;  // 64 rows x n_values fits the tile's 32-bit walk
-  int64_t blocks = (row_walk_waves(n_rows, n_values) + kThreads / 64 - 1) / (kThreads / 64);
-  if (blocks > 8192) blocks = 8192;
-  const dim3 grid(static_cast<uint32_t>(blocks));
-  if (spec.out_dt == in_dt) {
-    switch (dtype_size(in_dt)) {
-      case 1: hipLaunchKernelGGL(split_columns_raw_kernel<uint8_t>, grid, dim3(kThreads), 0, st, spec,
-                                 static_cast<const uint8_t*>(src), n_rows, n_values, ri); break;
-      case 2: hipLaunchKernelGGL(split_columns_raw_kernel<uint16_t>, grid, dim3(kThreads), 0, st, spec,
-                                 static_cast<const uint16_t*>(src), n_rows, n_values, ri); break;
-      case 4: hipLaunchKernelGGL(split_columns_raw_kernel<uint32_t>, grid, dim3(kThreads), 0, st, spec,
-                                 static_cast<const uint32_t*>(src), n_rows, n_values, ri); break;
-      case 8: hipLaunchKernelGGL(split_columns_raw_kernel<uint64_t>, grid, dim3(kThreads), 0, st, spec,
-                                 static_cast<const uint64_t*>(src), n_rows, n_values, ri); break;
-      default: return -1;
-    }
-    return static_cast<int>(hipGetLastError());
-  }
-#define DDL_SPLIT(TIN)                                                                                             \
-  do {                                                                                                             \
-    if (spec.out_dt == kBF16)                                                                                      \
-      hipLaunchKernelGGL((split_columns_kernel<TIN, kBF16>), grid, dim3(kThreads), 0, st, spec,                   \
-                         static_cast<const TIN*>(src), n_rows, n_values, ri);                                      \
-    else if (spec.out_dt == kF32)                                                                                  \
-      hipLaunchKernelGGL((split_columns_kernel<TIN, kF32>), grid, dim3(kThreads), 0, st, spec,                    \
-                         static_cast<const TIN*>(src), n_rows, n_values, ri);                                      \
-    else                                                                                                           \
-      return -1;                                                                                                   \
-  } while (0)
-  switch (in_dt) {
-    case kF32: DDL_SPLIT(float); break;
-    case kBF16: DDL_SPLIT(uint16_t); break;
-    case kU8: DDL_SPLIT(uint8_t); break;
-    default: return -1;
-  }
-#undef DDL_SPLIT
-  return static_cast<int>(hipGetLastError());
+  return launch_columns(spec, in_dt, n_rows, n_values, ri, [&](dim3 grid, auto in, auto out) {
+    using Tin = decltype(in);
+    hipLaunchKernelGGL((split_columns_kernel<Tin, decltype(out)>), grid, dim3(kThreads), 0, st, spec,
+                       static_cast<const Tin*>(src), n_rows, n_values, ri);
+  });
 }
 
 int pack_columns(const SplitSpec& spec, void* dst, int32_t in_dt, int64_t n_rows, int64_t n_values,
                  const RowIndex& ri, hipStream_t st) {
-  if (n_rows <= 0) return 0;
-  if (spec.n_groups < 1 || spec.n_groups > 8) return -2;
-  if (n_values < 1 || n_values > (1 << 24)) return -2;  // 64 rows x n_values fits the tile's 32-bit walk
-  int64_t blocks = (row_walk_waves(n_rows, n_values) + kThreads / 64 - 1) / (kThreads / 64);
-  if (blocks > 8192) blocks = 8192;
-  const dim3 grid(static_cast<uint32_t>(blocks));
-#define DDL_PACK(TIN, OUT)                                                                                        \
-  hipLaunchKernelGGL((pack_columns_kernel<TIN, OUT>), grid, dim3(kThreads), 0, st, spec, dst, n_rows, n_values, ri)
-  if (spec.out_dt == in_dt) {
-    switch (dtype_size(in_dt)) {
-      case 1: DDL_PACK(uint8_t, kRaw); break;
-      case 2: DDL_PACK(uint16_t, kRaw); break;
-      case 4: DDL_PACK(uint32_t, kRaw); break;
-      case 8: DDL_PACK(uint64_t, kRaw); break;
-      default: return -1;
-    }
-    return static_cast<int>(hipGetLastError());
-  }
-  if (spec.out_dt != kBF16 && spec.out_dt != kF32) return -1;
-  const bool bf = spec.out_dt == kBF16;
-  switch (in_dt) {
-    case kF32: if (bf) DDL_PACK(float, kBF16); else DDL_PACK(float, kF32); break;
-    case kBF16: if (bf) DDL_PACK(uint16_t, kBF16); else DDL_PACK(uint16_t, kF32); break;
-    case kU8: if (bf) DDL_PACK(uint8_t, kBF16); else DDL_PACK(uint8_t, kF32); break;
-    default: return -1;
-  }
-#undef DDL_PACK
-  return static_cast<int>(hipGetLastError());
+  return launch_columns(spec, in_dt, n_rows, n_values, ri, [&](dim3 grid, auto in, auto out) {
+    using Tout = decltype(out);
+    hipLaunchKernelGGL((pack_columns_kernel<decltype(in), Tout>), grid, dim3(kThreads), 0, st, spec,
+                       static_cast<Tout*>(dst), n_rows, n_values, ri);
+  });
 }
 
 }  // namespace ddl

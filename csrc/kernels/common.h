@@ -1,10 +1,14 @@
 // Shared device/host helpers for the ddl_amd CDNA4 (gfx950) kernels.
 #pragma once
 
-#include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#if defined(__HIPCC__)  // host check programs (csrc/kernels/tests) include this header without HIP
+#include <hip/hip_runtime.h>
 #define DDL_HD __host__ __device__ __forceinline__
+#else
+#define DDL_HD inline
+#endif
 
 namespace ddl {
 
@@ -64,9 +68,11 @@ DDL_HD int64_t source_row(const RowIndex& ri, int64_t r) {
   return ri.base + r;
 }
 
-// Host check every launcher that evaluates source_row(ri, 0 .. n) on the device makes first: a known mode, an index
-// vector in mode 1, no negative position, and in mode 2 every position inside the permutation's domain and the
-// domain inside the network's -- the cycle walk of feistel_perm terminates only on a bijection.
+// Host check every launcher whose kernels evaluate source_row(ri, 0 .. n) makes before it launches anything (the row
+// launchers of permute / collate / augment.hip and the token planners alike; a failure is the argument error -2):
+// a known mode, an index vector in mode 1, no negative position, and in mode 2 every position inside the
+// permutation's domain and the domain inside the network's -- the cycle walk of feistel_perm terminates only on a
+// bijection.
 inline bool row_index_ok(const RowIndex& ri, int64_t n) {
   if (ri.mode < 0 || ri.mode > 2) return false;
   if (ri.mode == 1 && n > 0 && !ri.idx) return false;
@@ -90,27 +96,6 @@ struct Affine {
   int32_t channels; // <= kMaxAffineChannels
   int32_t enabled;
 };
-
-// a / b for non-negative a < bound: 32-bit unsigned division when the bound fits (a short
-// v_rcp_iflag sequence), the 64-bit expansion otherwise. `bound` is a kernel argument, so the
-// branch is wave-uniform.
-__device__ __forceinline__ int64_t div_small(int64_t a, int64_t b, int64_t bound) {
-  if (bound <= static_cast<int64_t>(UINT32_MAX)) return static_cast<uint32_t>(a) / static_cast<uint32_t>(b);
-  return a / b;
-}
-
-// bf16 helpers: the plain cast lowers to v_cvt_pk_bf16_f32 (RNE, NaN-safe) at
-// -O3 on gfx950 (MI355X_MICROARCH "Correctness boundaries").
-__device__ __forceinline__ uint16_t f32_to_bf16_bits(float f) {
-  __bf16 b = static_cast<__bf16>(f);
-  return __builtin_bit_cast(uint16_t, b);
-}
-__device__ __forceinline__ float bf16_bits_to_f32(uint16_t u) {
-  return __builtin_bit_cast(float, static_cast<uint32_t>(u) << 16);
-}
-__device__ __forceinline__ uint32_t pack_bf16x2(float lo, float hi) {
-  return static_cast<uint32_t>(f32_to_bf16_bits(lo)) | (static_cast<uint32_t>(f32_to_bf16_bits(hi)) << 16);
-}
 
 // dtype codes shared with the Python side (ddl_amd/ops/_dtypes.py)
 enum DType : int32_t { kU8 = 0, kI32 = 1, kI64 = 2, kF16 = 3, kBF16 = 4, kF32 = 5 };

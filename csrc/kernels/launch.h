@@ -27,6 +27,8 @@ int feistel_indices(int64_t* out, int64_t count, int64_t base, const FeistelKeys
 // collate.hip ---------------------------------------------------------------
 // Image collate: src [B, H*W, C] (HWC, u8 / f32 / bf16) -> dst [B, C, H*W]
 // bf16 / f32 with out = x * scale[c] + bias[c]; rows gathered through ri.
+// Checked in this order, all before anything is launched: ri and channels (-2), the input then the output
+// dtype (-1), the LDS a tile needs (-5), the grid (-4).
 int collate_hwc_to_chw(void* dst, int32_t out_dt, const void* src, int32_t in_dt, int64_t batch, int64_t pixels,
                        int32_t channels, const RowIndex& ri, const Affine& aff, hipStream_t st);
 // Column-group split of a [n, nValues] row batch into up to 8 contiguous
@@ -67,6 +69,8 @@ struct AugmentSpec {
 struct CropBox {
   int32_t y, x, h, w, flip;
 };
+// Checked in this order, all before the boxes are drawn: ri (-2), boxes_out (-3), the geometry and path (-2), the
+// input then the output dtype (-1), the LDS path's budget (-5), the grid (-4). A refused call leaves boxes_out alone.
 int random_resized_crop(void* dst, int32_t out_dt, const void* src, int32_t in_dt, int64_t batch,
                         const AugmentSpec& a, int hwc, const RowIndex& ri, const Affine& aff, int32_t* boxes_out,
                         int path, hipStream_t st);
