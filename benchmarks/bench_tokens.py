@@ -57,8 +57,10 @@ def main(argv=None):
                          "are launches, with no host planning (in-order packing, fixed rows; the batch's counts "
                          "are device scalars)")
     ap.add_argument("--stream", action="store_true",
-                    help="resident: the token stream format (ResidentTokenStreamLoader): --batch counts ROWS per rank "
-                         "per step, cut from the concatenated shuffled documents; table, plan and pack are launches")
+                    help="resident / zerocopy: the token stream format (ResidentTokenStreamLoader; with --path zerocopy "
+                         "ZeroCopyTokenStreamLoader, whose gather_stream_pieces reads the plan's pieces from the "
+                         "registered corpus over PCIe): --batch counts ROWS per rank per step, cut from the "
+                         "concatenated shuffled documents; table, plan and pack are launches")
     ap.add_argument("--shuffle-rows", action="store_true",
                     help="with --stream: the epoch's rows in a shuffled order (shuffle_rows=True: the per-row plan "
                          "kernels in place of the contiguous plan)")
@@ -77,8 +79,8 @@ def main(argv=None):
         ap.error("--labels needs --path resident or zerocopy (the producer path has no labels output)")
     if a.plan != "host" and not resident:
         ap.error("--plan device needs --path resident")
-    if a.stream and (not resident or a.plan != "host" or a.mode != "pack"):
-        ap.error("--stream needs --path resident, and is neither --plan device nor --mode pad")
+    if a.stream and (not zc or a.plan != "host" or a.mode != "pack"):
+        ap.error("--stream needs --path resident or zerocopy, and is neither --plan device nor --mode pad")
     if a.shuffle_rows and not a.stream:
         ap.error("--shuffle-rows needs --stream")
     if a.mix and not a.stream:
@@ -134,8 +136,13 @@ def main(argv=None):
                 if a.mix:  # equal parts of the corpus, by document index
                     repeat = [float(r) for r in a.mix.split(",")]
                     mix = ddl_amd.TokenMix([round(p * a.n_seqs / len(repeat)) for p in range(len(repeat) + 1)], repeat)
-                dl = ddl_amd.ResidentTokenStreamLoader(source, gb, a.seq_len, env, labels=a.labels,
-                                                       shuffle_rows=a.shuffle_rows, mix=mix)
+                if resident:
+                    dl = ddl_amd.ResidentTokenStreamLoader(source, gb, a.seq_len, env, labels=a.labels,
+                                                           shuffle_rows=a.shuffle_rows, mix=mix)
+                else:
+                    dl = ddl_amd.ZeroCopyTokenStreamLoader(source, gb, a.seq_len, env, labels=a.labels,
+                                                           shuffle_rows=a.shuffle_rows, mix=mix,
+                                                           max_blocks=a.max_blocks)
                 dl.profile_every = a.kernel_sample
             elif resident:
                 dl = ddl_amd.ResidentTokenLoader(source, gb, a.seq_len, a.mode, env, pack_order=pack_order,
@@ -199,8 +206,9 @@ def main(argv=None):
                 real += int(dev_counts[0])
                 rows += int(dev_counts[1])
             st = dl.stats()
-            timing = dl.timing() if resident else None  # of the measured phase and its warm-up
-            if resident:
+            timed = resident or a.stream  # the loaders with a launch frame
+            timing = dl.timing() if timed else None  # of the measured phase and its warm-up
+            if timed:
                 dl.profile_every = 0
             if env.world_size > 1:
                 t = torch.tensor([dt], dtype=torch.float64)
@@ -264,6 +272,18 @@ def main(argv=None):
                 elif zc:
                     per_path = {"path": "zerocopy", "max_blocks": st["max_blocks"], "host_waits": st["host_waits"],
                                 "prefault_s": round(st["prefault_s"], 3)}
+                    if a.stream:
+                        per_path.update(plan="stream", format="stream", handoff=st["handoff"],
+                                        host_us_per_step=round(timing["host_us_per_step"], 1),
+                                        kernel_us=None if timing["kernel_us"] is None
+                                        else round(timing["kernel_us"], 1),
+                                        kernel_samples=timing["kernel_samples"], hbm_bytes=st["hbm_bytes"],
+                                        max_segments=st["max_segments"], tables_built=st["tables_built"],
+                                        shuffle_rows=st["shuffle_rows"], mix=a.mix, mix_parts=st["mix_parts"],
+                                        mix_documents=st["mix_documents"], orders_built=st["orders_built"],
+                                        epoch_prep_us=None if timing["epoch_prep_us"] is None
+                                        else round(timing["epoch_prep_us"], 1),
+                                        epoch_prep_samples=timing["epoch_prep_samples"])
                 else:
                     per_path = {
                         "producers": a.producers, "host_threads": a.host_threads, "slots": a.slots,

@@ -25,6 +25,7 @@
 #include "launch.h"
 #include "ragged_index.h"
 #include "tokens_indexed.h"
+#include "tokens_stream_gather.h"
 #include "engine.h"
 #include "stager.h"
 
@@ -930,6 +931,20 @@ PYBIND11_MODULE(_ddl_hip, m) {
       },
       py::arg("dst"), py::arg("src"), py::arg("src_start"), py::arg("dst_offsets"), py::arg("tile_start"), py::arg("n"),
       py::arg("n_tiles"), py::arg("elem_bytes"), py::arg("max_blocks"), py::arg("stream"));
+  m.def(
+      "gather_stream_pieces",
+      [](uintptr_t dst, uintptr_t src, int64_t corpus_elems, uintptr_t seg_src, uintptr_t seg_offsets, uintptr_t counts,
+         int64_t max_segs, int64_t rows, int64_t seq_len, int elem_bytes, int64_t max_blocks, uintptr_t stream) {
+        check_rc(ddl::gather_stream_pieces(as_ptr<void>(dst), as_ptr<const void>(src), corpus_elems,
+                                           as_ptr<const int64_t>(seg_src), as_ptr<const int64_t>(seg_offsets),
+                                           as_ptr<const int64_t>(counts), max_segs, rows, seq_len, elem_bytes,
+                                           max_blocks, as_stream(stream)),
+                 "gather_stream_pieces");
+      },
+      py::arg("dst"), py::arg("src"), py::arg("corpus_elems"), py::arg("seg_src"), py::arg("seg_offsets"),
+      py::arg("counts"), py::arg("max_segs"), py::arg("rows"), py::arg("seq_len"), py::arg("elem_bytes"),
+      py::arg("max_blocks"), py::arg("stream"));
+  m.attr("STREAM_GATHER_CHUNK_BYTES") = ddl::kSgChunkBytes;
   m.def("pack_plan_scratch_ints",&ddl::pack_plan_scratch_ints, py::arg("max_segs"), py::arg("max_rows"));
   m.def(
       "pack_plan_device",

@@ -287,6 +287,20 @@ int gather_ragged(void* dst, const void* src, const int64_t* src_start, const in
                   const int32_t* tile_start, int64_t n, int64_t n_tiles, int elem_bytes, int64_t max_blocks,
                   hipStream_t st);
 
+// tokens_stream_gather.hip --------------------------------------------------
+// The tokens of a stream plan (StreamPlanOut of either plan kernel: seg_src [max_segs], seg_offsets [max_segs + 1],
+// counts) copied into the flat window dst [rows * seq_len] of elem_bytes = 2 or 4 byte elements in HBM:
+// dst[g] = src[seg_src[s] + g - seg_offsets[s]] for seg_offsets[s] <= g < seg_offsets[s + 1], s < n_seg = counts[1];
+// positions at or past seg_offsets[n_seg] are not written, and a plan with counts[0] < 0, n_seg = 0 or n_seg >
+// max_segs writes nothing. src: HBM or pinned, device-mapped host memory of corpus_elems elements (16-byte aligned
+// non-temporal loads of the pieces' aligned hulls; a piece outside [0, corpus_elems) is not dereferenced). The grid is
+// static -- the chunks of rows * seq_len elements, the kernel reads the counts -- and max_blocks > 0 caps it.
+// pad_pack_tokens_indexed renders the batch from dst with corpus = dst, corpus_elems = rows * seq_len and seg_src =
+// seg_offsets.
+int gather_stream_pieces(void* dst, const void* src, int64_t corpus_elems, const int64_t* seg_src,
+                         const int64_t* seg_offsets, const int64_t* counts, int64_t max_segs, int64_t rows,
+                         int64_t seq_len, int elem_bytes, int64_t max_blocks, hipStream_t st);
+
 // bucket.hip ----------------------------------------------------------------
 // Owner bucketing of a global batch for the resident loader's exchange: positions
 // [pos0, pos0 + count) of the Feistel permutation `keys`, sample idx owned by rank

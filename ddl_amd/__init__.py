@@ -22,6 +22,7 @@ __all__ = [
     "ZeroCopyTokenLoader",
     "ResidentTokenLoader",
     "ResidentTokenStreamLoader",
+    "ZeroCopyTokenStreamLoader",
     "TokenMix",
     "DataLoader",
     "OutputSpec",
@@ -58,6 +59,10 @@ def __getattr__(name):
         from .token_stream import ResidentTokenStreamLoader
 
         return ResidentTokenStreamLoader
+    if name == "ZeroCopyTokenStreamLoader":
+        from .zerocopy_stream import ZeroCopyTokenStreamLoader
+
+        return ZeroCopyTokenStreamLoader
     if name == "DataLoader":
         from .frontend import DataLoader
 

@@ -42,7 +42,8 @@ class CorpusReplica:
         if nbytes > hbm_fraction * free:
             raise DDLError(f"the corpus ({nbytes} bytes) exceeds hbm_fraction={hbm_fraction} of the free HBM "
                            f"({free} bytes free, {int(hbm_fraction * free)} allowed); a corpus is not sharded across "
-                           "ranks: use ZeroCopyTokenLoader, which reads it from host memory")
+                           "ranks: use ZeroCopyTokenLoader (batches of sequences) or ZeroCopyTokenStreamLoader (the "
+                           "stream format), which read it from host memory")
         t0 = time.perf_counter()
         hip = _native.hip()
         hbm = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
@@ -84,14 +85,19 @@ class ResidentCorpusLoader:
 
     _replica = None
 
-    def _attach_replica(self, hbm_fraction: float, chunk_bytes: int) -> bool:
-        """The fields every resident loader reports, and on the GPU the replica. True on the GPU."""
-        self.replica_shared = False
-        self.load_s = 0.0
+    def _init_frame(self) -> None:
+        """The fields of the launch frame and its timings (a loader that reads the corpus where it lies, such as
+        ``ZeroCopyTokenStreamLoader``, uses the frame without a replica)."""
         self.assemble_s = 0.0  # wall time spent in _assemble (host_us_per_step of the benchmark)
         self.profile_every = 0  # > 0: device events around the launches of every profile_every-th step
         self._kernel_evs: list = []
         self._selectors: dict = {}
+
+    def _attach_replica(self, hbm_fraction: float, chunk_bytes: int) -> bool:
+        """The fields every resident loader reports, and on the GPU the replica. True on the GPU."""
+        self.replica_shared = False
+        self.load_s = 0.0
+        self._init_frame()
         if self.prep_stream is None:
             return False
         self._replica, self.replica_shared = CorpusReplica.acquire(

@@ -1552,9 +1552,12 @@ def _stream_plan_layout(plan_ptr: int, rows: int, max_segs: int) -> tuple[int, i
 
 def _launch_stream_emit(h, whole: torch.Tensor, plan: tuple, *, corpus_ptr: int, corpus_elems: int, tok16: bool,
                         rows: int, seq_len: int, pad_id: int, max_segs: int, position_dtype, stream: int,
-                        labels: bool, ignore_index: int, plan_fn, plan_kw: dict) -> dict:
+                        labels: bool, ignore_index: int, plan_fn, plan_kw: dict, staging_ptr: int = 0,
+                        max_blocks: int = 0) -> dict:
     """``plan_fn(counts=..., **plan_kw)`` and ``pad_pack_tokens_indexed`` over the plan it wrote (pack mode, counts
-    read from device memory), with everything returned carved from ``whole``."""
+    read from device memory), with everything returned carved from ``whole``. ``staging_ptr``: the zero-copy form
+    (``launch_stream_plan_zerocopy``) -- ``gather_stream_pieces`` between the two copies the batch's tokens from the
+    corpus into that window, which the emit launch then reads as its corpus."""
     S, R, M = int(seq_len), int(rows), int(max_segs)
     o_ss, o_so, o_rs, o_re, _ = plan
     out_b = token_output_bytes(R, S, M, position_dtype, labels)
@@ -1562,6 +1565,13 @@ def _launch_stream_emit(h, whole: torch.Tensor, plan: tuple, *, corpus_ptr: int,
     counts = whole[out_b:out_b + 32].view(torch.int64)
     c_ptr = counts.data_ptr()
     plan_fn(counts=c_ptr, **plan_kw)
+    if staging_ptr:
+        h.gather_stream_pieces(dst=staging_ptr, src=corpus_ptr, corpus_elems=corpus_elems, seg_src=o_ss,
+                               seg_offsets=o_so, counts=c_ptr, max_segs=M, rows=R, seq_len=S,
+                               elem_bytes=2 if tok16 else 4, max_blocks=int(max_blocks), stream=stream)
+        # piece s starts at window element seg_offsets[s]: the plan's seg_offsets are the window's seg_src. A label
+        # is the next token of the same row and segment (ti_labels4): the emit reads nothing outside the window
+        corpus_ptr, corpus_elems, o_ss = staging_ptr, R * S, o_so
     h.pad_pack_tokens_indexed(
         corpus=corpus_ptr, corpus_elems=corpus_elems, src_start=0, seg_src=o_ss, offsets=0, row_start=o_rs,
         row_end=o_re, seg_offsets=o_so, n_seg=0, out_tokens=ids.data_ptr(), attn_mask=mask.data_ptr(),
@@ -1580,13 +1590,13 @@ def launch_stream_plan(plan_ptr: int, whole: torch.Tensor, *, corpus_ptr: int, c
                        corpus_offsets_ptr: int, n_corpus: int, table_ptr: int, selector: dict, row_base: int,
                        rows: int, seq_len: int, pad_id: int, max_segs: int, position_dtype=torch.int64,
                        stream: int = 0, labels: bool = False, ignore_index: int = -100,
-                       n: int | None = None) -> dict:
+                       n: int | None = None, staging_ptr: int = 0, max_blocks: int = 0) -> dict:
     """The two launches of one token stream batch on raw stream ``stream``: ``token_stream_plan`` and
     ``pad_pack_tokens_indexed`` (pack mode, counts read from device memory). ``plan_ptr`` / ``whole``: the two
     sizes of ``token_stream_bytes``, 16-byte aligned device memory; ``selector``: the ``RowIndex`` of the epoch's
     order with base 0, the one ``table_ptr``'s table was built with; ``n``: the order's length where it is not the
     corpus's document count (an explicit order). Nothing here allocates, copies or synchronises. Returns the dict of
-    ``stream_tokens_indexed_device``."""
+    ``stream_tokens_indexed_device``. ``staging_ptr`` / ``max_blocks``: ``launch_stream_plan_zerocopy``'s."""
     h = _native.hip()
     S, R, M = int(seq_len), int(rows), int(max_segs)
     ignore_index = check_ignore_index(labels, ignore_index)
@@ -1597,14 +1607,16 @@ def launch_stream_plan(plan_ptr: int, whole: torch.Tensor, *, corpus_ptr: int, c
                    seg_offsets=o_so, seg_src=o_ss, row_start=o_rs, row_end=o_re, stream=stream, **selector)
     return _launch_stream_emit(h, whole, plan, corpus_ptr=corpus_ptr, corpus_elems=corpus_elems, tok16=tok16, rows=R,
                                seq_len=S, pad_id=pad_id, max_segs=M, position_dtype=position_dtype, stream=stream,
-                               labels=labels, ignore_index=ignore_index, plan_fn=h.token_stream_plan, plan_kw=plan_kw)
+                               labels=labels, ignore_index=ignore_index, plan_fn=h.token_stream_plan, plan_kw=plan_kw,
+                               staging_ptr=staging_ptr, max_blocks=max_blocks)
 
 
 def launch_stream_plan_rows(plan_ptr: int, whole: torch.Tensor, *, corpus_ptr: int, corpus_elems: int, tok16: bool,
                             corpus_offsets_ptr: int, n_corpus: int, table_ptr: int, selector: dict,
                             row_selector: dict, stream_rows: int, rows: int, seq_len: int, pad_id: int,
                             max_segs: int, position_dtype=torch.int64, stream: int = 0, labels: bool = False,
-                            ignore_index: int = -100, n: int | None = None) -> dict:
+                            ignore_index: int = -100, n: int | None = None, staging_ptr: int = 0,
+                            max_blocks: int = 0) -> dict:
     """``launch_stream_plan`` for rows picked anywhere in the stream: the two launches of ``token_stream_plan_rows``
     and ``pad_pack_tokens_indexed``, the call it is for contiguous rows. ``plan_ptr``: the plan size of
     ``token_stream_bytes(..., shuffled_rows=True)``; ``row_selector``: the ``RowIndex`` arguments that select the
@@ -1623,7 +1635,117 @@ def launch_stream_plan_rows(plan_ptr: int, whole: torch.Tensor, *, corpus_ptr: i
     return _launch_stream_emit(h, whole, plan, corpus_ptr=corpus_ptr, corpus_elems=corpus_elems, tok16=tok16, rows=R,
                                seq_len=S, pad_id=pad_id, max_segs=M, position_dtype=position_dtype, stream=stream,
                                labels=labels, ignore_index=ignore_index, plan_fn=h.token_stream_plan_rows,
-                               plan_kw=plan_kw)
+                               plan_kw=plan_kw, staging_ptr=staging_ptr, max_blocks=max_blocks)
+
+
+def stream_staging_bytes(rows: int, seq_len: int, token_bytes: int) -> int:
+    """Bytes of the staging window of one zero-copy token stream batch: ``rows * seq_len`` ids of the corpus's
+    width, what ``gather_stream_pieces`` writes and the emit launch reads."""
+    return _align16(int(rows) * int(seq_len) * int(token_bytes))
+
+
+def stream_zerocopy_window_bytes(rows: int, seq_len: int, max_segs: int, token_bytes: int,
+                                 shuffled_rows: bool = False) -> int:
+    """Bytes of a zero-copy stream batch's window between its launches: the plan of ``token_stream_bytes`` and,
+    behind it, the staging window (``stream_staging_bytes``)."""
+    plan, _ = token_stream_bytes(rows, seq_len, max_segs, shuffled_rows=shuffled_rows)
+    return plan + stream_staging_bytes(rows, seq_len, token_bytes)
+
+
+def launch_stream_plan_zerocopy(plan_ptr: int, whole: torch.Tensor, *, max_blocks: int = 0, **kw) -> dict:
+    """``launch_stream_plan`` for a corpus the emit launch should not read token by token -- pinned, device-mapped
+    host memory, where every load instruction is a PCIe read: ``token_stream_plan``, ``gather_stream_pieces`` (the
+    batch's tokens, in 16-byte aligned loads, into a staging window in HBM; ``max_blocks`` > 0 caps its grid) and
+    ``pad_pack_tokens_indexed`` out of that window, on one raw stream. ``plan_ptr``: device memory of
+    ``stream_zerocopy_window_bytes`` bytes; ``corpus_ptr`` is the address the device reads the corpus at. The other
+    arguments, the result and the promise -- nothing here allocates, copies or synchronises -- are
+    ``launch_stream_plan``'s."""
+    plan_b, _ = token_stream_bytes(kw["rows"], kw["seq_len"], kw["max_segs"])
+    return launch_stream_plan(plan_ptr, whole, staging_ptr=plan_ptr + plan_b, max_blocks=max_blocks, **kw)
+
+
+def launch_stream_plan_rows_zerocopy(plan_ptr: int, whole: torch.Tensor, *, max_blocks: int = 0, **kw) -> dict:
+    """``launch_stream_plan_zerocopy`` for rows picked anywhere in the stream (``launch_stream_plan_rows``);
+    ``plan_ptr``: ``stream_zerocopy_window_bytes(..., shuffled_rows=True)`` bytes."""
+    plan_b, _ = token_stream_bytes(kw["rows"], kw["seq_len"], kw["max_segs"], shuffled_rows=True)
+    return launch_stream_plan_rows(plan_ptr, whole, staging_ptr=plan_ptr + plan_b, max_blocks=max_blocks, **kw)
+
+
+def _stream_pieces_args(src, seg_src, seg_offsets, counts, rows: int, seq_len: int):
+    flat = (src.cpu if isinstance(src, HostRows) else src).reshape(-1)
+    if flat.element_size() not in (2, 4):
+        raise TypeError("gather_stream_pieces: 2- or 4-byte elements")
+    for name, t in (("seg_src", seg_src), ("seg_offsets", seg_offsets), ("counts", counts)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int64 or not t.is_contiguous():
+            raise TypeError(f"gather_stream_pieces: {name} must be a contiguous int64 tensor")
+    M = int(seg_src.numel())
+    if M < 1 or seg_offsets.numel() < M + 1 or counts.numel() < 2:
+        raise ValueError("gather_stream_pieces: seg_src [max_segs >= 1], seg_offsets [max_segs + 1], counts [>= 2]")
+    if int(rows) < 1 or int(seq_len) < 1 or int(rows) * int(seq_len) > 0x7FFFFFFF:
+        raise ValueError("gather_stream_pieces: rows and seq_len must be >= 1 and rows * seq_len fit int32")
+    return flat, M
+
+
+def ref_gather_stream_pieces(src, seg_src, seg_offsets, counts, rows: int, seq_len: int,
+                             out: torch.Tensor | None = None) -> torch.Tensor:
+    """The definition of ``gather_stream_pieces``, in NumPy on the CPU: a copy of ``out`` (zeros without one) of
+    ``rows * seq_len`` elements with ``out[g] = src[seg_src[s] + g - seg_offsets[s]]`` for ``seg_offsets[s] <= g <
+    seg_offsets[s + 1]``, ``s < n_seg = counts[1]``, ``g < min(seg_offsets[n_seg], min(counts[0], rows) *
+    seq_len)``. Nothing is written for ``counts[0] < 0``, ``n_seg`` = 0 or ``n_seg > len(seg_src)``, nor for a piece
+    whose source range is not inside the source."""
+    flat, M = _stream_pieces_args(src, seg_src, seg_offsets, counts, rows, seq_len)
+    a = flat.cpu().numpy()
+    ss, so, c = seg_src.cpu().numpy(), seg_offsets.cpu().numpy(), counts.cpu().numpy()
+    n = int(rows) * int(seq_len)
+    res = np.zeros(n, dtype=a.dtype) if out is None else out.detach().cpu().reshape(-1)[:n].numpy().copy()
+    n_rows, n_seg = int(c[0]), int(c[1])
+    if n_rows > 0 and 0 < n_seg <= M:
+        limit = min(int(so[n_seg]), min(n_rows, int(rows)) * int(seq_len))
+        for s in range(n_seg):
+            lo, hi, e0 = int(so[s]), int(so[s + 1]), int(ss[s])
+            if e0 < 0 or e0 + (hi - lo) > a.size:
+                continue
+            g1 = min(hi, limit)
+            if g1 > lo:
+                res[lo:g1] = a[e0:e0 + (g1 - lo)]
+    return torch.from_numpy(res)
+
+
+def gather_stream_pieces(src, seg_src: torch.Tensor, seg_offsets: torch.Tensor, counts: torch.Tensor, rows: int,
+                         seq_len: int, *, out: torch.Tensor | None = None, max_blocks: int = 0,
+                         stream=None) -> torch.Tensor:
+    """The tokens of a token stream plan as one flat window (``ref_gather_stream_pieces``, the definition): ``src``
+    is the corpus, a flat device tensor or ``HostRows`` (pinned, device-mapped host memory: every token of the batch
+    crosses PCIe once, in 16-byte aligned loads) of 2- or 4-byte elements; ``seg_src`` [max_segs], ``seg_offsets``
+    [max_segs + 1] and ``counts`` are the device arrays ``token_stream_plan`` / ``token_stream_plan_rows`` wrote. One
+    launch of a static grid (the kernel reads the counts), no copy, no synchronisation; ``out``: ``rows * seq_len``
+    elements of the source's dtype on the device, whose positions at or past the plan's tokens keep what they held
+    (allocated here, uninitialised, without one). ``max_blocks`` > 0 caps the grid. CPU tensors take the
+    reference."""
+    if not _is_gpu(src):
+        res = ref_gather_stream_pieces(src, seg_src, seg_offsets, counts, rows, seq_len, out)
+        if out is not None:
+            out.reshape(-1)[:res.numel()].copy_(res)
+            return out.reshape(-1)[:res.numel()]
+        return res
+    flat, M = _stream_pieces_args(src, seg_src, seg_offsets, counts, rows, seq_len)
+    if isinstance(src, torch.Tensor) and not src.is_contiguous():
+        raise ValueError("gather_stream_pieces: source must be contiguous")
+    n, dev = int(rows) * int(seq_len), seg_src.device
+    for name, t in (("seg_src", seg_src), ("seg_offsets", seg_offsets), ("counts", counts)):
+        if not t.is_cuda or t.device != dev or (isinstance(src, torch.Tensor) and t.device != src.device):
+            raise ValueError(f"gather_stream_pieces: {name} must live on the source's GPU")
+    handle, tstream = _stream_pair(stream, dev)
+    if out is None:
+        with torch.cuda.stream(tstream):
+            out = torch.empty(n, dtype=flat.dtype, device=dev)
+    elif not out.is_cuda or not out.is_contiguous() or out.dtype != flat.dtype or out.numel() < n:
+        raise ValueError("gather_stream_pieces: bad out tensor")
+    _native.hip().gather_stream_pieces(
+        dst=out.data_ptr(), src=_src_addr(src), corpus_elems=flat.numel(), seg_src=seg_src.data_ptr(),
+        seg_offsets=seg_offsets.data_ptr(), counts=counts.data_ptr(), max_segs=M, rows=int(rows),
+        seq_len=int(seq_len), elem_bytes=flat.element_size(), max_blocks=int(max_blocks), stream=handle)
+    return out.reshape(-1)[:n]
 
 
 def stream_tokens_indexed_device(corpus: torch.Tensor, corpus_offsets: torch.Tensor, table: torch.Tensor | None = None,

@@ -10,8 +10,8 @@ depends on how many ranks share a socket. Here
   registered (shared with any zero-copy loader over it), copied with SDMA and unregistered again. The offsets
   stay on the host, where the plan is built. At W > 1 every rank loads its own full replica, with no
   collective; a corpus larger than ``hbm_fraction`` of the free HBM is refused (sharding is not supported: use
-  ``ZeroCopyTokenLoader``). Loaders over one corpus on one device (train + eval) share one replica, counted per
-  process and freed when the last one closes;
+  ``ZeroCopyTokenLoader``, or ``ZeroCopyTokenStreamLoader`` for the stream format). Loaders over one corpus on
+  one device (train + eval) share one replica, counted per process and freed when the last one closes;
 * per step the host does what ``ZeroCopyTokenLoader`` does minus the tile plan: this rank's ``EpochOrder``
   indices, the lengths, the producer's FFD rule, the native ``pack_plan`` -- written as a
   ``TokenWindowLayout(k=1)`` header plus ``src_start`` / ``seg_src`` into a slot of a small pinned ring;

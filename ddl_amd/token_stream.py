@@ -23,6 +23,9 @@ launches, no copy, no host read of device memory, no synchronisation per step or
 kept, since prefetch crosses the epoch boundary; everything is ordered by the prep stream). ``ops.ref_stream_tokens``
 is the definition; with ``device="cpu"`` the loader runs it and gives the same dict.
 
+``TokenStreamLoader`` holds everything of this that does not depend on where the tokens lie; for a corpus that does
+not fit in HBM ``zerocopy_stream.ZeroCopyTokenStreamLoader`` delivers the same batches out of pinned host memory.
+
 ``shuffle_rows=True`` adds the sample shuffle of the format (Megatron's ``shuffle_idx``): in stream order every
 document longer than ``S`` puts all its pieces into neighbouring rows of one step. Global batch ``g`` of epoch
 ``e`` is then rows ``rho_e(g * GB + j)``, ``j < GB`` (rank ``r`` takes ``j`` in ``[r * LB, (r + 1) * LB)``), with
@@ -68,23 +71,29 @@ class _RowOrder:
         self.batches_per_epoch = rows_per_epoch // global_batch
 
 
-class ResidentTokenStreamLoader(ResidentCorpusLoader, PrefetchedIndexedLoader):
-    def __init__(self, source: SharedTokenSource, global_batch: int, seq_len: int = 4096, env: DDLEnv | None = None,
-                 *, seed: int = 0, shuffle: bool = True, pad_id: int = 0, depth: int = 2,
-                 device: str | torch.device | None = None, n_epochs: int | None = None,
-                 resume_state: dict | None = None, handoff: str = "device", hbm_fraction: float = 0.8,
-                 chunk_bytes: int = 256 << 20, max_segments: int | None = None, labels: bool = False,
-                 ignore_index: int = -100, shuffle_rows: bool = False, mix: TokenMix | None = None):
-        """``global_batch`` counts rows. ``max_segments``: the capacity of a batch's ``cu_seqlens`` (default
-        ``ops.stream_max_segments``, which no window of any order exceeds; a smaller one that a batch overflows
-        gives that batch as padding with ``n_rows`` = -1). ``shuffle_rows``: the rows of an epoch in the order of
-        a second permutation (see the module's text); ``shuffle=False`` with it gives shuffled rows of the
-        unshuffled stream. ``mix``: a ``TokenMix`` over all the corpus's documents (``mix.bounds[-1] ==
-        n_documents``): the epoch's documents are its weighted order. The extra documents of a fractional repeat
-        are the same in every epoch, so ``total_tokens`` -- the tokens of one epoch, computed here once -- and
-        with it the rows and batches per epoch and the checkpoint cursor are constants; the default
-        ``max_segments`` is ``ops.stream_max_segments`` over the lengths with every document counted
-        ``mix.max_copies`` times, a multiset that holds every epoch's documents."""
+class TokenStreamLoader(ResidentCorpusLoader, PrefetchedIndexedLoader):
+    """What the loaders of the stream format share: the epoch's order, tables and selectors, the step, the
+    ``kind="token_stream"`` checkpoint. A loader says where the device reads the corpus and its offsets
+    (``_corpus_ptr``, ``_offsets_dev``), which launch path renders a step (``_launch_plan`` / ``_launch_plan_rows``
+    with ``_launch_kw``) and how large a step's window between the launches is (``_window_bytes``)."""
+
+    _launch_plan = staticmethod(launch_stream_plan)
+    _launch_plan_rows = staticmethod(launch_stream_plan_rows)
+    _corpus_ptr = 0        # the address the device reads the corpus's tokens at
+    _offsets_dev = None    # the corpus offsets in HBM
+
+    def _launch_kw(self) -> dict:
+        return {}
+
+    def _window_bytes(self) -> int:
+        return self._plan_bytes
+
+    def _init_stream(self, source: SharedTokenSource, global_batch: int, seq_len: int, env: DDLEnv | None, *,
+                     seed: int, shuffle: bool, pad_id: int, depth: int, device, n_epochs: int | None,
+                     resume_state: dict | None, handoff: str, max_segments: int | None, labels: bool,
+                     ignore_index: int, shuffle_rows: bool, mix: TokenMix | None) -> None:
+        """The arguments checked, the epoch's sizes, the cursor and the prep stream: everything in front of the
+        corpus itself."""
         if handoff not in ("device", "host"):
             raise ValueError("handoff must be 'device' or 'host'")
         self.labels, self.ignore_index = bool(labels), check_ignore_index(labels, ignore_index)
@@ -134,34 +143,31 @@ class ResidentTokenStreamLoader(ResidentCorpusLoader, PrefetchedIndexedLoader):
         self.tables_built = self.orders_built = 0
         self._epoch_evs: list = []
         self._windows: list = []
-        if not self._attach_replica(hbm_fraction, chunk_bytes):
-            return
-        try:
-            n = self.n_order
-            scratch = _native.hip().token_stream_table_scratch(n)
-            table_bytes = 8 * (2 * (n + 1) + scratch + (2 * n if mix is not None else 0))
-            free, _ = torch.cuda.mem_get_info(self.device)
-            if table_bytes > float(hbm_fraction) * free:
-                raise DDLError(f"the two epoch tables{' and orders' if mix is not None else ''} ({table_bytes} bytes) "
-                               f"exceed hbm_fraction={hbm_fraction} of the free HBM ({free} bytes free)")
-            self._replica.offsets(self._offs_t, self.prep_stream)
-            with streams.on_stream(self.prep_stream):
-                # two tables: prefetch crosses the epoch boundary (epoch e lives in slot e % 2)
-                self._tables = [torch.empty(n + 1, dtype=torch.int64, device=self.device) for _ in range(2)]
-                self._scratch = torch.empty(scratch, dtype=torch.int64, device=self.device)
-                self._table_epoch = [None, None]
-                if mix is not None:  # the epochs' document orders, slot for slot with the tables
-                    self._orders = [torch.empty(n, dtype=torch.int64, device=self.device) for _ in range(2)]
-                    self._order_sel = [row_selector(o) for o in self._orders]
-                    self._mix_args = mix.device_args(self.seed, self.order.shuffle)
-                self._plan_bytes, self._batch_bytes = token_stream_bytes(self.LB, self.seq_len, self.max_segments,
-                                                                         labels=self.labels,
-                                                                         shuffled_rows=self.shuffle_rows)
-                self._windows = [torch.empty(self._plan_bytes, dtype=torch.uint8, device=self.device)
-                                 for _ in range(self.depth + 1)]
-        except Exception:
-            self.close()
-            raise
+
+    def _table_bytes(self) -> int:
+        """Bytes of the two epoch tables, the scan's scratch and (a mix) the two orders."""
+        n = self.n_order
+        scratch = _native.hip().token_stream_table_scratch(n)
+        return 8 * (2 * (n + 1) + scratch + (2 * n if self.mix is not None else 0))
+
+    def _init_tables(self) -> None:
+        """The two tables, the orders of a mix and the ring of windows, on the prep stream."""
+        n, mix = self.n_order, self.mix
+        scratch = _native.hip().token_stream_table_scratch(n)
+        with streams.on_stream(self.prep_stream):
+            # two tables: prefetch crosses the epoch boundary (epoch e lives in slot e % 2)
+            self._tables = [torch.empty(n + 1, dtype=torch.int64, device=self.device) for _ in range(2)]
+            self._scratch = torch.empty(scratch, dtype=torch.int64, device=self.device)
+            self._table_epoch = [None, None]
+            if mix is not None:  # the epochs' document orders, slot for slot with the tables
+                self._orders = [torch.empty(n, dtype=torch.int64, device=self.device) for _ in range(2)]
+                self._order_sel = [row_selector(o) for o in self._orders]
+                self._mix_args = mix.device_args(self.seed, self.order.shuffle)
+            self._plan_bytes, self._batch_bytes = token_stream_bytes(self.LB, self.seq_len, self.max_segments,
+                                                                     labels=self.labels,
+                                                                     shuffled_rows=self.shuffle_rows)
+            self._windows = [torch.empty(self._window_bytes(), dtype=torch.uint8, device=self.device)
+                             for _ in range(self.depth + 1)]
 
     # ---------------------------------------------------------------- order
     def _perm(self, epoch: int) -> FeistelPermutation | None:
@@ -199,7 +205,7 @@ class ResidentTokenStreamLoader(ResidentCorpusLoader, PrefetchedIndexedLoader):
                                  stream=self.prep_stream.cuda_stream)
                 self.orders_built += 1
             _native.hip().token_stream_table(
-                corpus_offsets=self._replica.offsets_dev.data_ptr(), n_corpus=self.n_documents, n=self.n_order,
+                corpus_offsets=self._offsets_dev.data_ptr(), n_corpus=self.n_documents, n=self.n_order,
                 table=self._tables[k].data_ptr(), tile_sums=self._scratch.data_ptr(),
                 stream=self.prep_stream.cuda_stream, **sel)
             if timed:
@@ -224,18 +230,17 @@ class ResidentTokenStreamLoader(ResidentCorpusLoader, PrefetchedIndexedLoader):
             table = self._table(e, sel)
 
             def issue(win, whole):
-                rep = self._replica
                 common = dict(
-                    corpus_ptr=rep.hbm.data_ptr(), corpus_elems=self.n_elems,
-                    tok16=self.source.token_bytes == 2, corpus_offsets_ptr=rep.offsets_dev.data_ptr(),
+                    corpus_ptr=self._corpus_ptr, corpus_elems=self.n_elems,
+                    tok16=self.source.token_bytes == 2, corpus_offsets_ptr=self._offsets_dev.data_ptr(),
                     n_corpus=self.n_documents, n=self.n_order, table_ptr=table.data_ptr(), selector=sel,
                     rows=self.LB, seq_len=self.seq_len, pad_id=self.pad_id, max_segs=self.max_segments,
-                    stream=st.cuda_stream, labels=self.labels, ignore_index=self.ignore_index)
+                    stream=st.cuda_stream, labels=self.labels, ignore_index=self.ignore_index, **self._launch_kw())
                 if self.shuffle_rows:
-                    return launch_stream_plan_rows(
+                    return self._launch_plan_rows(
                         win.data_ptr(), whole, stream_rows=self.order.n_samples,
                         row_selector=dict(self._selector(e, self._row_perm), base=row_base), **common)
-                return launch_stream_plan(win.data_ptr(), whole, row_base=row_base, **common)
+                return self._launch_plan(win.data_ptr(), whole, row_base=row_base, **common)
 
             r, ev = self._launch(t, self._batch_bytes, issue)
         counts = r.pop("counts")
@@ -287,15 +292,6 @@ class ResidentTokenStreamLoader(ResidentCorpusLoader, PrefetchedIndexedLoader):
             self.epoch, self.cursor = self.epoch + 1, 0
 
     # ---------------------------------------------------------------- misc
-    def stats(self) -> dict:
-        return {"batches": self.batches, "source_bytes": self.nbytes, "load_s": self.load_s,
-                "load_gbps": self.nbytes / self.load_s / 1e9 if self.load_s > 0 else 0.0, "handoff": self.handoff,
-                "host_waits": self.host_waits, "replica_shared": self.replica_shared, "format": "stream",
-                "rows_per_epoch": self.order.n_samples, "max_segments": self.max_segments,
-                "tables_built": self.tables_built, "shuffle_rows": self.shuffle_rows,
-                "mix_parts": self.mix.parts if self.mix is not None else 0, "mix_documents": self.n_order,
-                "orders_built": self.orders_built}
-
     def timing(self) -> dict:
         """``ResidentCorpusLoader.timing`` and ``epoch_prep_us``: the mean device time of an epoch's own launches
         (``token_mix_order`` with a mix, and the table scan) over the epochs begun while ``profile_every`` > 0."""
@@ -307,7 +303,8 @@ class ResidentTokenStreamLoader(ResidentCorpusLoader, PrefetchedIndexedLoader):
             out["epoch_prep_us"] = 1e3 * sum(a.elapsed_time(b) for a, b in evs) / len(evs)
         return out
 
-    def close(self) -> None:
+    def _close_stream(self) -> None:
+        """Drain the prep stream and drop the queue, the windows, the tables and the orders."""
         if getattr(self, "prep_stream", None) is not None:
             self.prep_stream.synchronize()
         if hasattr(self, "_queue"):
@@ -315,10 +312,59 @@ class ResidentTokenStreamLoader(ResidentCorpusLoader, PrefetchedIndexedLoader):
         self._kernel_evs = []
         self._windows = []
         self._tables = self._scratch = self._orders = None
-        self._release_replica()
 
     def __del__(self):  # pragma: no cover - best effort
         try:
             self.close()
         except Exception:
             pass
+
+
+class ResidentTokenStreamLoader(TokenStreamLoader):
+    def __init__(self, source: SharedTokenSource, global_batch: int, seq_len: int = 4096, env: DDLEnv | None = None,
+                 *, seed: int = 0, shuffle: bool = True, pad_id: int = 0, depth: int = 2,
+                 device: str | torch.device | None = None, n_epochs: int | None = None,
+                 resume_state: dict | None = None, handoff: str = "device", hbm_fraction: float = 0.8,
+                 chunk_bytes: int = 256 << 20, max_segments: int | None = None, labels: bool = False,
+                 ignore_index: int = -100, shuffle_rows: bool = False, mix: TokenMix | None = None):
+        """``global_batch`` counts rows. ``max_segments``: the capacity of a batch's ``cu_seqlens`` (default
+        ``ops.stream_max_segments``, which no window of any order exceeds; a smaller one that a batch overflows
+        gives that batch as padding with ``n_rows`` = -1). ``shuffle_rows``: the rows of an epoch in the order of
+        a second permutation (see the module's text); ``shuffle=False`` with it gives shuffled rows of the
+        unshuffled stream. ``mix``: a ``TokenMix`` over all the corpus's documents (``mix.bounds[-1] ==
+        n_documents``): the epoch's documents are its weighted order. The extra documents of a fractional repeat
+        are the same in every epoch, so ``total_tokens`` -- the tokens of one epoch, computed here once -- and
+        with it the rows and batches per epoch and the checkpoint cursor are constants; the default
+        ``max_segments`` is ``ops.stream_max_segments`` over the lengths with every document counted
+        ``mix.max_copies`` times, a multiset that holds every epoch's documents."""
+        self._init_stream(source, global_batch, seq_len, env, seed=seed, shuffle=shuffle, pad_id=pad_id, depth=depth,
+                          device=device, n_epochs=n_epochs, resume_state=resume_state, handoff=handoff,
+                          max_segments=max_segments, labels=labels, ignore_index=ignore_index,
+                          shuffle_rows=shuffle_rows, mix=mix)
+        if not self._attach_replica(hbm_fraction, chunk_bytes):
+            return
+        try:
+            table_bytes = self._table_bytes()
+            free, _ = torch.cuda.mem_get_info(self.device)
+            if table_bytes > float(hbm_fraction) * free:
+                raise DDLError(f"the two epoch tables{' and orders' if mix is not None else ''} ({table_bytes} bytes) "
+                               f"exceed hbm_fraction={hbm_fraction} of the free HBM ({free} bytes free)")
+            self._offsets_dev = self._replica.offsets(self._offs_t, self.prep_stream)
+            self._corpus_ptr = self._replica.hbm.data_ptr()
+            self._init_tables()
+        except Exception:
+            self.close()
+            raise
+
+    def stats(self) -> dict:
+        return {"batches": self.batches, "source_bytes": self.nbytes, "load_s": self.load_s,
+                "load_gbps": self.nbytes / self.load_s / 1e9 if self.load_s > 0 else 0.0, "handoff": self.handoff,
+                "host_waits": self.host_waits, "replica_shared": self.replica_shared, "format": "stream",
+                "rows_per_epoch": self.order.n_samples, "max_segments": self.max_segments,
+                "tables_built": self.tables_built, "shuffle_rows": self.shuffle_rows,
+                "mix_parts": self.mix.parts if self.mix is not None else 0, "mix_documents": self.n_order,
+                "orders_built": self.orders_built}
+
+    def close(self) -> None:
+        self._close_stream()
+        self._release_replica()

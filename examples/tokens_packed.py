@@ -42,6 +42,11 @@ stream by a second permutation, so the pieces of a long document no longer sit i
 parts as there are numbers, and a document of part ``p`` appears ``repeat[p]`` times per epoch (a fraction: that
 share of the part's documents once more, the same ones every epoch).
 
+``--zero-copy --stream`` delivers the same format from a corpus that stays in host memory
+(``ZeroCopyTokenStreamLoader``): only the offsets are uploaded, each batch's pieces are read over PCIe by
+``gather_stream_pieces`` and the batches, ``--shuffle-rows``, ``--mix``, ``--labels`` and the checkpoint are those of
+``--resident --stream``.
+
 ``--labels`` (with ``--resident`` or ``--zero-copy``) asks the loader for the next-token targets as well
 (``labels=True``: int64 ``labels``, ``-100`` where a position has no target -- the end of a row or of a segment,
 padding) and trains a toy embedding + linear model on every batch with ``cross_entropy(ignore_index=-100)``.
@@ -75,12 +80,12 @@ def main() -> None:
                     help="with --resident: the batch's order and pack plan are built on the GPU too (in-order "
                          "packing, static shapes, counts as device scalars)")
     ap.add_argument("--stream", action="store_true",
-                    help="with --resident: full rows cut from the concatenated shuffled documents "
+                    help="with --resident or --zero-copy: full rows cut from the concatenated shuffled documents "
                          "(--global-batch counts rows)")
     ap.add_argument("--shuffle-rows", action="store_true",
-                    help="with --resident --stream: the epoch's rows in a shuffled order (shuffle_rows=True)")
+                    help="with --stream: the epoch's rows in a shuffled order (shuffle_rows=True)")
     ap.add_argument("--mix", default=None, metavar="R0,R1,...",
-                    help="with --resident --stream: repeats of equal parts of the corpus, e.g. 2,1,0.5 (TokenMix)")
+                    help="with --stream: repeats of equal parts of the corpus, e.g. 2,1,0.5 (TokenMix)")
     ap.add_argument("--labels", action="store_true",
                     help="with --resident or --zero-copy: the loader also delivers next-token labels, and every "
                          "batch runs a tiny embedding -> linear -> cross_entropy step on them")
@@ -92,12 +97,13 @@ def main() -> None:
         ap.error("--zero-copy and --resident are two loaders: pick one")
     if a.device_plan and not a.resident:
         ap.error("--device-plan is a mode of --resident")
-    if a.stream and (not a.resident or a.device_plan or a.mode != "pack"):
-        ap.error("--stream is a format of --resident (packed rows by construction; it has no --device-plan mode)")
+    if a.stream and (not (a.resident or a.zero_copy) or a.device_plan or a.mode != "pack"):
+        ap.error("--stream is a format of --resident and --zero-copy (packed rows by construction; it has no "
+                 "--device-plan mode)")
     if a.shuffle_rows and not a.stream:
-        ap.error("--shuffle-rows is an option of --resident --stream")
+        ap.error("--shuffle-rows is an option of --stream")
     if a.mix and not a.stream:
-        ap.error("--mix is an option of --resident --stream")
+        ap.error("--mix is an option of --stream")
     if a.labels and not (a.zero_copy or a.resident):
         ap.error("--labels needs --resident or --zero-copy (the producer path does not deliver labels)")
     vocab = a.vocab or (512 if a.labels else 50257)
@@ -123,8 +129,9 @@ def main() -> None:
                     repeat = [float(r) for r in a.mix.split(",")]
                     bounds = [round(p * a.n_seqs / len(repeat)) for p in range(len(repeat) + 1)]
                     mix = ddl_amd.TokenMix(bounds, repeat)
-                dl = ddl_amd.ResidentTokenStreamLoader(src, a.global_batch, a.seq_len, env, n_epochs=a.epochs,
-                                                       shuffle_rows=a.shuffle_rows, mix=mix, **lab_kw)
+                stream_cls = ddl_amd.ResidentTokenStreamLoader if a.resident else ddl_amd.ZeroCopyTokenStreamLoader
+                dl = stream_cls(src, a.global_batch, a.seq_len, env, n_epochs=a.epochs, shuffle_rows=a.shuffle_rows,
+                                mix=mix, **lab_kw)
                 if mix is not None and env.rank == 0:
                     print(f"mix: {mix.parts} parts x {list(mix.repeat)} -> {mix.n_order} documents and "
                           f"{dl.total_tokens} tokens per epoch (the corpus: {a.n_seqs} documents)", flush=True)
