@@ -35,7 +35,10 @@ def main(argv=None):
                     help="pack mode: exact packed rows per batch, or the window layout's fixed max rows (padding)")
     ap.add_argument("--dispatch", default="auto", choices=["auto", "inline", "lookahead", "window", "python"])
     ap.add_argument("--mode", default="pack", choices=["pad", "pack"])
-    ap.add_argument("--pack-order", default="ffd", choices=["in_order", "ffd"],
+    ap.add_argument("--max-rows", type=int, default=None,
+                    help="--path resident --plan device --mode pack: the static row count of every batch "
+                         "(default: the worst case)")
+    ap.add_argument("--pack-order", default="ffd", choices=["in_order", "ffd", "ffd_device"],
                     help="pack mode: first-fit-decreasing rows (measured 93%% dense) or in-order (~75%%)")
     ap.add_argument("--idle-steps", type=int, default=200,
                     help="phase 2: steps of a fixed-cost token train step, for GPU idle %% (0 disables)")
@@ -86,9 +89,12 @@ def main(argv=None):
     if a.mix and not a.stream:
         ap.error("--mix needs --stream")
     if a.plan == "device" and a.mode == "pack":
-        if a.pack_order != "in_order":
-            ap.error("--plan device builds the in-order plan: pass --pack-order in_order")
+        if a.pack_order == "ffd":
+            ap.error("--plan device builds the in-order plan (--pack-order in_order) or, with one more kernel, the "
+                     "first-fit-decreasing one (--pack-order ffd_device)")
         a.token_rows = "fixed"
+    elif a.pack_order == "ffd_device" or a.max_rows is not None:
+        ap.error("--pack-order ffd_device and --max-rows need --path resident --plan device --mode pack")
 
     import torch
     import torch.distributed as dist
@@ -147,7 +153,7 @@ def main(argv=None):
             elif resident:
                 dl = ddl_amd.ResidentTokenLoader(source, gb, a.seq_len, a.mode, env, pack_order=pack_order,
                                                  token_rows=a.token_rows, n_epochs=n_epochs, plan=a.plan,
-                                                 labels=a.labels)
+                                                 labels=a.labels, max_rows=a.max_rows)
                 dl.profile_every = a.kernel_sample
             elif zc:
                 dl = ddl_amd.ZeroCopyTokenLoader(source, gb, a.seq_len, a.mode, env, pack_order=pack_order,
@@ -206,6 +212,21 @@ def main(argv=None):
                 real += int(dev_counts[0])
                 rows += int(dev_counts[1])
             st = dl.stats()
+            ffd_kernel_us = None
+            if pack_order == "ffd_device" and dev.type == "cuda":
+                # the new launch alone, between device events, over this rank's first batches of epoch 0
+                offs_dev = source.offsets.tensor().view(-1).to(dev)
+                evs = []
+                for g in range(32):  # the epoch's batches, round and round
+                    g %= a.n_seqs // gb
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    ops.ffd_index_device(offs_dev, perm=dl.order.perm(0), base=g * gb + env.rank * a.batch,
+                                         count=a.batch, seq_len=a.seq_len)
+                    e1.record()
+                    evs.append((e0, e1))
+                sync()
+                ffd_kernel_us = round(1e3 * sum(x.elapsed_time(y) for x, y in evs[4:]) / max(1, len(evs) - 4), 1)
             timed = resident or a.stream  # the loaders with a launch frame
             timing = dl.timing() if timed else None  # of the measured phase and its warm-up
             if timed:
@@ -261,6 +282,9 @@ def main(argv=None):
                                 "kernel_samples": timing["kernel_samples"],
                                 "load_s": round(st["load_s"], 3), "load_gbps": round(st["load_gbps"], 2),
                                 "replica_shared": st["replica_shared"], "plan": "stream" if a.stream else a.plan}
+                    if pack_order == "ffd_device" or a.max_rows is not None:
+                        per_path.update(max_rows=a.max_rows, ffd_kernel_us=ffd_kernel_us,
+                                        static_rows=int(delivered // (a.steps * a.seq_len * env.world_size)))
                     if a.stream:
                         per_path.update(format="stream", max_segments=st["max_segments"],
                                         tables_built=st["tables_built"], shuffle_rows=st["shuffle_rows"],

@@ -24,6 +24,7 @@
 #include "common.h"
 #include "launch.h"
 #include "ragged_index.h"
+#include "tokens_ffd.h"
 #include "tokens_indexed.h"
 #include "tokens_stream_gather.h"
 #include "engine.h"
@@ -814,6 +815,25 @@ PYBIND11_MODULE(_ddl_hip, m) {
       py::arg("n_domain"), py::arg("half_bits"), py::arg("n"), py::arg("seq_len"), py::arg("max_segs"),
       py::arg("src_start"), py::arg("offsets"), py::arg("seg_src"), py::arg("counts"), py::arg("pad_counts"),
       py::arg("stream"));
+  m.attr("FFD_MAX_SEQS") = static_cast<int64_t>(ddl::kFfdMaxSeqs);
+  m.def(
+      "token_ffd_order",
+      [](uintptr_t corpus_offsets, int64_t n_corpus, int mode, uintptr_t idx, int64_t base, std::vector<uint64_t> keys,
+         uint64_t n_domain, uint32_t half_bits, int64_t n, int64_t seq_len, uintptr_t index_out, uintptr_t counts,
+         uintptr_t stream) {
+        ddl::FfdOrderSpec sp{};
+        sp.corpus_offsets = as_ptr<const int64_t>(corpus_offsets);
+        sp.n_corpus = n_corpus;
+        sp.ri = make_index(mode, idx, base, keys, n_domain, half_bits);
+        sp.n = n;
+        sp.seq_len = seq_len;
+        sp.index_out = as_ptr<int64_t>(index_out);
+        sp.counts = as_ptr<int64_t>(counts);
+        check_rc(ddl::token_ffd_order(sp, as_stream(stream)), "token_ffd_order");
+      },
+      py::arg("corpus_offsets"), py::arg("n_corpus"), py::arg("mode"), py::arg("idx"), py::arg("base"), py::arg("keys"),
+      py::arg("n_domain"), py::arg("half_bits"), py::arg("n"), py::arg("seq_len"), py::arg("index_out"),
+      py::arg("counts"), py::arg("stream"));
   m.def("token_stream_table_scratch", &ddl::token_stream_table_scratch, py::arg("n"));
   m.def(
       "token_stream_table",

@@ -181,6 +181,24 @@ struct BatchDescSpec {
 };
 int token_batch_descriptor(const BatchDescSpec& spec, hipStream_t st);
 
+// tokens_ffd.hip ------------------------------------------------------------
+// The first-fit-decreasing order of a token batch, built on the device (one workgroup; tokens_ffd.h): of the n
+// sequences the selector names (as BatchDescSpec names them, lengths by the same rules), index_out [n] = their
+// corpus indices in the order of ffd_if_it_wins -- the first-fit-decreasing order when it packs rows of seq_len
+// tokens into fewer rows than the given order does, else the given order -- and counts = [ffd_rows,
+// in_order_rows, used (1: the FFD order, 0: the given one)]. token_batch_descriptor then takes index_out as an
+// explicit index. n <= kFfdMaxSeqs (4096), else -2. n = 0 writes only the counts.
+struct FfdOrderSpec {
+  const int64_t* corpus_offsets;  // [n_corpus + 1], device
+  int64_t n_corpus;
+  RowIndex ri;
+  int64_t n;
+  int64_t seq_len;
+  int64_t* index_out;  // [n]
+  int64_t* counts;     // [3]
+};
+int token_ffd_order(const FfdOrderSpec& spec, hipStream_t st);
+
 // tokens_stream.hip ---------------------------------------------------------
 // The token stream of an epoch: concat(document q_0 .. q_{n-1}), q_k = source_row(ri, k) (the Feistel order of
 // the epoch, an explicit device index, or the identity), cut into rows of seq_len tokens.

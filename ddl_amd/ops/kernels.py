@@ -1061,14 +1061,17 @@ def pack_tokens_indexed(corpus: torch.Tensor, corpus_offsets, idx, seq_len: int,
 
 
 # ------------------------------- tokens out of an HBM corpus, planned on the device
-def device_plan_bytes(n: int, max_segs: int | None = None, max_rows: int = 0) -> int:
+def device_plan_bytes(n: int, max_segs: int | None = None, max_rows: int = 0, ffd: bool = False) -> int:
     """Bytes of the plan arrays the device-planned ops keep between their launches (``max_segs`` None: pad mode):
     src_start [n], offsets [n + 1], and in pack mode seg_src [max_segs], seg_offsets [max_segs + 1], row_start /
-    row_end [max_rows] and the plan kernel's scratch. Nothing a caller holds lives here."""
+    row_end [max_rows] and the plan kernel's scratch; with ``ffd`` (pack mode) the index [n] and the three counts of
+    ``token_ffd_order`` behind them. Nothing a caller holds lives here."""
     total = _align16(8 * n) + _align16(8 * (n + 1))
     if max_segs is not None:
         total += (_align16(8 * max_segs) + _align16(8 * (max_segs + 1)) + 2 * _align16(8 * max_rows)
                   + _align16(4 * (2 * (max_segs + 1) + max_rows + 1)))  # == pack_plan_scratch_ints
+        if ffd:
+            total += _align16(8 * n) + 32
     return total
 
 
@@ -1083,9 +1086,10 @@ def device_batch_bytes(rows: int, seq_len: int, max_segs: int | None = None, pos
 def launch_device_plan(plan_ptr: int, whole: torch.Tensor, *, corpus_ptr: int, corpus_elems: int, tok16: bool,
                        corpus_offsets_ptr: int, n_corpus: int, selector: dict, n: int, seq_len: int, pad_id: int,
                        pack: bool, max_segs: int = 0, max_rows: int = 0, position_dtype=torch.int64,
-                       stream: int = 0, labels: bool = False, ignore_index: int = -100) -> dict:
-    """The launches of one device-planned batch on raw stream ``stream``: descriptor, (pack mode) plan, pack.
-    ``plan_ptr``: ``device_plan_bytes`` of 16-byte aligned device memory for the plan arrays; ``whole``:
+                       stream: int = 0, labels: bool = False, ignore_index: int = -100, ffd: bool = False) -> dict:
+    """The launches of one device-planned batch on raw stream ``stream``: descriptor, (pack mode) plan, pack; with
+    ``ffd`` (pack mode, ``device_plan_bytes(..., ffd=True)``) ``token_ffd_order`` in front, and the descriptor runs
+    on its index. ``plan_ptr``: ``device_plan_bytes`` of 16-byte aligned device memory for the plan arrays; ``whole``:
     ``device_batch_bytes`` of uint8 device memory the outputs and the counts are carved from; ``selector``: the
     ``mode / idx / base / keys / n_domain / half_bits`` of a ``RowIndex``. Nothing here allocates, copies or
     synchronises. Returns the dict of ``pack_tokens_indexed_device`` / ``pad_tokens_indexed_device``
@@ -1121,6 +1125,11 @@ def launch_device_plan(plan_ptr: int, whole: torch.Tensor, *, corpus_ptr: int, c
         ids, mask, pos, seg, cu, *lab = carve_token_outputs(whole, R, S, M, position_dtype, labels)
         counts = whole[out_b:out_b + 32].view(torch.int64)
         c_ptr = counts.data_ptr()
+        if ffd and n:  # n = 0: nothing to order (the descriptor reads no index)
+            o_idx = o_scr + _align16(4 * (2 * (M + 1) + R + 1))
+            h.token_ffd_order(corpus_offsets=corpus_offsets_ptr, n_corpus=n_corpus, n=n, seq_len=S, index_out=o_idx,
+                              counts=o_idx + _align16(8 * n), stream=stream, **selector)
+            selector = dict(mode=1, idx=o_idx, base=0, keys=[0] * 6, n_domain=1, half_bits=1)
         h.token_batch_descriptor(corpus_offsets=corpus_offsets_ptr, n_corpus=n_corpus, n=n, seq_len=S, max_segs=M,
                                  src_start=o_src, offsets=o_off, seg_src=o_ss, counts=c_ptr, pad_counts=False,
                                  stream=stream, **selector)
@@ -1139,26 +1148,15 @@ def launch_device_plan(plan_ptr: int, whole: torch.Tensor, *, corpus_ptr: int, c
     return r
 
 
-def _device_plan_args(corpus, corpus_offsets, index, perm, base, count, seq_len, position_dtype):
-    """Checked (flat corpus, offsets, n) of a device-planned op."""
-    if position_dtype not in (torch.int64, torch.int32):
-        raise TypeError("position_dtype must be int64 or int32")
-    if not isinstance(corpus, torch.Tensor) or (corpus.dtype != torch.int32 and corpus.dtype not in _TOK16):
-        raise TypeError("corpus must be a flat int32 / 16-bit token tensor")
-    if not isinstance(corpus_offsets, torch.Tensor) or corpus_offsets.dtype != torch.int64:
-        raise TypeError("corpus_offsets must be an int64 tensor")
-    if not corpus.is_contiguous() or not corpus_offsets.is_contiguous():
-        raise ValueError("corpus and corpus_offsets must be contiguous")
-    if corpus_offsets.device != corpus.device:
-        raise ValueError("corpus_offsets must be on the corpus's device")
-    if int(seq_len) <= 0:
-        raise ValueError("seq_len must be > 0")
+def _selection_args(corpus_offsets, index, perm, base, count) -> tuple[torch.Tensor, int]:
+    """Checked (flat offsets, n) of a selection of corpus sequences: a device ``index``, or positions ``[base, base +
+    count)`` of ``perm`` or of the identity."""
     offs = corpus_offsets.reshape(-1)
     if offs.numel() < 1:
         raise ValueError("corpus_offsets needs at least one entry")
     if index is not None and perm is not None:
         raise ValueError("give either index or perm, not both")
-    if index is not None and (index.dtype != torch.int64 or index.device != corpus.device
+    if index is not None and (index.dtype != torch.int64 or index.device != corpus_offsets.device
                               or not index.is_contiguous()):
         raise ValueError("index must be a contiguous int64 tensor on the corpus's device")
     if index is not None and count is not None and int(count) != index.numel():
@@ -1176,6 +1174,24 @@ def _device_plan_args(corpus, corpus_offsets, index, perm, base, count, seq_len,
         raise IndexError("perm positions out of range, or a permutation domain larger than the corpus")
     if index is None and perm is None and int(base) + n > n_corpus:
         raise IndexError("identity rows out of range")
+    return offs, n
+
+
+def _device_plan_args(corpus, corpus_offsets, index, perm, base, count, seq_len, position_dtype):
+    """Checked (flat corpus, offsets, n) of a device-planned op."""
+    if position_dtype not in (torch.int64, torch.int32):
+        raise TypeError("position_dtype must be int64 or int32")
+    if not isinstance(corpus, torch.Tensor) or (corpus.dtype != torch.int32 and corpus.dtype not in _TOK16):
+        raise TypeError("corpus must be a flat int32 / 16-bit token tensor")
+    if not isinstance(corpus_offsets, torch.Tensor) or corpus_offsets.dtype != torch.int64:
+        raise TypeError("corpus_offsets must be an int64 tensor")
+    if not corpus.is_contiguous() or not corpus_offsets.is_contiguous():
+        raise ValueError("corpus and corpus_offsets must be contiguous")
+    if corpus_offsets.device != corpus.device:
+        raise ValueError("corpus_offsets must be on the corpus's device")
+    if int(seq_len) <= 0:
+        raise ValueError("seq_len must be > 0")
+    offs, n = _selection_args(corpus_offsets, index, perm, base, count)
     return corpus.reshape(-1), offs, n
 
 
@@ -1197,12 +1213,78 @@ def _ref_selected(offs: torch.Tensor, n: int, index, perm, base) -> np.ndarray:
     return _ref_rows(offs.numel() - 1, n, index, perm, int(base)).numpy()
 
 
+FFD_MAX_SEQS = 4096  # kFfdMaxSeqs (csrc/kernels/tokens_ffd.h): the bins of token_ffd_order's 64 x 64 tree
+
+
+def check_ffd_count(n: int) -> None:
+    if int(n) > FFD_MAX_SEQS:
+        raise ValueError(f"the device first-fit-decreasing order takes at most {FFD_MAX_SEQS} sequences per batch, "
+                         f"not {int(n)}: use the host plan (pack_order='ffd') for larger batches")
+
+
+def ref_ffd_index(offsets, n: int, index=None, perm=None, base: int = 0, *, seq_len: int):
+    """The definition of ``token_ffd_order``: ``(index int64 [n], ffd_rows, in_order_rows, used)`` for the ``n``
+    selected sequences of the corpus with these ``offsets``. Lengths follow the batch descriptor (an index outside
+    the corpus, or offsets that decrease, give an empty sequence); ``index`` is the selection in first-fit-decreasing
+    order (``ffd_order_py``) when that packs rows of ``seq_len`` tokens into fewer rows than the given order does
+    (``in_order_rows_py``), else the selection as given -- ``ffd_if_it_wins``, in NumPy, no native code."""
+    from ..models.tokens import ffd_order_py, in_order_rows_py
+
+    offs = offsets.cpu().numpy() if isinstance(offsets, torch.Tensor) else np.asarray(offsets)
+    offs = offs.reshape(-1).astype(np.int64)
+    if index is not None:
+        q = index.to("cpu", torch.int64).numpy() if isinstance(index, torch.Tensor) else np.asarray(index, np.int64)
+    else:
+        q = _ref_rows(len(offs) - 1, int(n), None, perm, int(base)).numpy()
+    q = q.reshape(-1)
+    ok = (q >= 0) & (q < len(offs) - 1)
+    qq = np.where(ok, q, 0)
+    lens = np.where(ok, np.maximum(offs[qq + 1] - offs[qq], 0), 0) if len(offs) > 1 else np.zeros(len(q), np.int64)
+    order, ffd_rows = ffd_order_py(lens, int(seq_len))
+    in_order = in_order_rows_py(lens, int(seq_len))
+    used = int(ffd_rows < in_order)
+    return torch.from_numpy(q[order] if used else q.copy()), int(ffd_rows), int(in_order), used
+
+
+def ffd_index_device(corpus_offsets: torch.Tensor, *, index: torch.Tensor | None = None,
+                     perm: FeistelPermutation | None = None, base: int = 0, count: int | None = None, seq_len: int,
+                     out: torch.Tensor | None = None, stream=None) -> dict:
+    """The ``pack_order="ffd"`` rule of the token paths (``ffd_if_it_wins``) with nothing computed on the host: of the
+    sequences selected as ``pack_tokens_indexed_device`` selects them (at most ``FFD_MAX_SEQS``), ``index`` = their
+    corpus indices (int64 [n]) in first-fit-decreasing order when that order packs rows of ``seq_len`` tokens into
+    fewer rows than the given one, else as given, and ``counts`` = int64 ``[ffd_rows, in_order_rows, used]``. One
+    launch of one workgroup (``token_ffd_order``); no copy, no synchronisation. ``out``: an int64 device tensor of
+    ``n + 3`` entries both are carved from. CPU tensors take the reference path (``ref_ffd_index``)."""
+    if not isinstance(corpus_offsets, torch.Tensor) or corpus_offsets.dtype != torch.int64:
+        raise TypeError("corpus_offsets must be an int64 tensor")
+    if not corpus_offsets.is_contiguous():
+        raise ValueError("corpus_offsets must be contiguous")
+    if int(seq_len) <= 0:
+        raise ValueError("seq_len must be > 0")
+    offs, n = _selection_args(corpus_offsets, index, perm, base, count)
+    check_ffd_count(n)
+    if not offs.is_cuda:
+        idx, ffd_rows, in_order, used = ref_ffd_index(offs, n, index, perm, base, seq_len=seq_len)
+        return {"index": idx, "counts": torch.tensor([ffd_rows, in_order, used], dtype=torch.int64)}
+    handle, stream = _stream_pair(stream, offs.device)
+    if out is None:
+        with torch.cuda.stream(stream):
+            out = torch.empty(n + 3, dtype=torch.int64, device=offs.device)
+    elif out.dtype != torch.int64 or out.device != offs.device or out.numel() < n + 3 or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous int64 tensor of {n + 3} entries on the offsets' device")
+    out = out.view(-1)
+    _native.hip().token_ffd_order(corpus_offsets=offs.data_ptr(), n_corpus=offs.numel() - 1, n=n, seq_len=int(seq_len),
+                                  index_out=out.data_ptr(), counts=out.data_ptr() + 8 * n, stream=handle,
+                                  **(_index_kw(index, perm, base) if n else _index_kw(None, None, 0)))
+    return {"index": out[:n], "counts": out[n:n + 3]}
+
+
 def pack_tokens_indexed_device(corpus: torch.Tensor, corpus_offsets: torch.Tensor, *,
                                index: torch.Tensor | None = None, perm: FeistelPermutation | None = None,
                                base: int = 0, count: int | None = None, seq_len: int, pad_id: int = 0,
                                position_dtype=torch.int64, max_rows: int | None = None, max_segs: int | None = None,
                                out: torch.Tensor | None = None, stream=None, labels: bool = False,
-                               ignore_index: int = -100) -> dict:
+                               ignore_index: int = -100, pack_order: str = "in_order") -> dict:
     """``pack_tokens_indexed`` with nothing computed on the host: ``corpus`` (flat int32 / 16-bit ids) and
     ``corpus_offsets`` (int64 [n_corpus + 1]) are device tensors, and the sequences are selected as ``gather_rows``
     selects rows -- a device ``index``, or positions ``[base, base + count)`` of ``perm`` (evaluated inline by the
@@ -1219,13 +1301,26 @@ def pack_tokens_indexed_device(corpus: torch.Tensor, corpus_offsets: torch.Tenso
     bytes that everything is carved from, else one allocation. ``labels=True`` adds ``labels`` (int64, the
     next-token labels of ``ref_token_labels``, written by the pack launch; all ``ignore_index`` for an overflowed
     plan) and both byte counts take ``labels=True``. CPU tensors take the reference path (``ref_gather_ragged`` +
-    ``ref_pack_plan`` + ``ref_pack_tokens``): the same dict."""
+    ``ref_pack_plan`` + ``ref_pack_tokens``): the same dict.
+
+    ``pack_order="ffd"`` packs the selected sequences in the order of ``ffd_index_device`` (first-fit-decreasing
+    when it needs fewer rows, at most ``FFD_MAX_SEQS`` sequences): one more launch, ``token_ffd_order``, in front of
+    the three, which then run on its index; the plan window (``device_plan_bytes(..., ffd=True)``) also holds that
+    index and its counts. The dict is the same. The CPU path applies ``ref_ffd_index`` first."""
     flat, offs, n = _device_plan_args(corpus, corpus_offsets, index, perm, base, count, seq_len, position_dtype)
     ignore_index = check_ignore_index(labels, ignore_index)
+    if pack_order not in ("in_order", "ffd"):
+        raise ValueError("pack_order must be 'in_order' or 'ffd'")
+    ffd = pack_order == "ffd"
+    if ffd:
+        check_ffd_count(n)
     S = int(seq_len)
     M, R = _device_plan_caps(n, flat.numel(), S, max_rows, max_segs)
     if not flat.is_cuda:
-        tokens, dofs = ref_gather_ragged(flat, offs, _ref_selected(offs, n, index, perm, base))
+        sel = _ref_selected(offs, n, index, perm, base)
+        if ffd:
+            sel = ref_ffd_index(offs, n, index, perm, base, seq_len=S)[0].numpy()
+        tokens, dofs = ref_gather_ragged(flat, offs, sel)
         rs, re_, so = ref_pack_plan(dofs.numpy(), S)
         n_seg, n_tokens = len(so) - 1, int(dofs[-1])
         ok = n_seg <= M and len(rs) <= R
@@ -1241,7 +1336,7 @@ def pack_tokens_indexed_device(corpus: torch.Tensor, corpus_offsets: torch.Tenso
         if labels:
             r["labels"] = ref_token_labels(ids, mask, seg, ignore_index)
         return r
-    plan_b = device_plan_bytes(n, M, R)
+    plan_b = device_plan_bytes(n, M, R, ffd=ffd)
     handle, stream = _stream_pair(stream, flat.device)
     with torch.cuda.stream(stream):
         buf = _token_out_buffer(out, plan_b + device_batch_bytes(R, S, M, position_dtype, labels), flat.device)
@@ -1250,7 +1345,7 @@ def pack_tokens_indexed_device(corpus: torch.Tensor, corpus_offsets: torch.Tenso
         tok16=flat.dtype in _TOK16, corpus_offsets_ptr=offs.data_ptr(), n_corpus=offs.numel() - 1,
         selector=_index_kw(index, perm, base) if n else _index_kw(None, None, 0), n=n, seq_len=S, pad_id=pad_id,
         pack=True, max_segs=M, max_rows=R,
-        position_dtype=position_dtype, stream=handle, labels=labels, ignore_index=ignore_index)
+        position_dtype=position_dtype, stream=handle, labels=labels, ignore_index=ignore_index, ffd=ffd)
 
 
 def pad_tokens_indexed_device(corpus: torch.Tensor, corpus_offsets: torch.Tensor, *,

@@ -30,6 +30,14 @@ epoch's Feistel round keys and issues launches -- ``token_batch_descriptor`` (in
 each segment's corpus element), ``pack_plan_device`` and ``pad_pack_tokens_indexed`` reading the plan's counts
 from device memory. No NumPy, no pinned slot, no H2D copy, no host read of anything the device wrote; the shapes
 are therefore static and the counts of a batch are 0-d device tensors (``docs/ARCHITECTURE.md``).
+
+``plan="device", mode="pack", pack_order="ffd_device"`` adds the producer's FFD rule to that path without bringing
+the host back: one more launch, ``token_ffd_order`` (one workgroup: lengths, a sort and a first-fit placement in
+LDS), writes the batch's corpus indices in first-fit-decreasing order when that needs fewer rows, and the three
+launches run on that index. The batches are those of ``plan="host", pack_order="ffd", token_rows="fixed"``, at most
+``ops.FFD_MAX_SEQS`` sequences per rank and step. ``max_rows`` (device pack plan only) makes every batch that many
+rows instead of the worst case ``layout.max_segments``, so the denser plan reaches the model as a smaller static
+shape; a batch that needs more comes back as padding with ``n_rows = -1`` (the plan kernel's overflow contract).
 """
 
 from __future__ import annotations
@@ -40,7 +48,8 @@ import torch
 from . import _native
 from .corpus_replica import ResidentCorpusLoader
 from .models.tokens import SharedTokenSource, check_token_options, drop_cached_views
-from .ops.kernels import (carve_token_outputs, device_batch_bytes, device_plan_bytes, launch_device_plan,
+from .ops.kernels import (carve_token_outputs, check_ffd_count, device_batch_bytes, device_plan_bytes,
+                          launch_device_plan,
                           pack_tokens_indexed_device, pad_tokens_indexed_device, segment_sources,
                           token_output_bytes)
 from .token_plan import HostPlannedTokenLoader
@@ -54,9 +63,20 @@ class ResidentTokenLoader(ResidentCorpusLoader, HostPlannedTokenLoader):
                  token_rows: str | None = None, pad_id: int = 0, depth: int = 2,
                  device: str | torch.device | None = None, n_epochs: int | None = None,
                  resume_state: dict | None = None, handoff: str = "device", hbm_fraction: float = 0.8,
-                 chunk_bytes: int = 256 << 20, plan: str = "host", labels: bool = False, ignore_index: int = -100):
+                 chunk_bytes: int = 256 << 20, plan: str = "host", labels: bool = False, ignore_index: int = -100,
+                 max_rows: int | None = None):
         if plan not in ("host", "device"):
             raise ValueError("plan must be 'host' or 'device'")
+        ffd_device = pack_order == "ffd_device"
+        if ffd_device:
+            if plan != "device" or mode != "pack":
+                raise ValueError("pack_order='ffd_device' is the first-fit-decreasing order built by a kernel: it "
+                                 "needs plan='device', mode='pack' (with plan='host' use pack_order='ffd')")
+            pack_order = "in_order"  # what the shared checks and the host-side planner know
+            check_ffd_count(int(global_batch) // (env or DDLEnv()).world_size)  # the batch of one rank
+        if max_rows is not None and (plan != "device" or mode != "pack" or int(max_rows) < 1):
+            raise ValueError("max_rows (>= 1) is the static row count of plan='device', mode='pack' batches; the "
+                             "other paths size their batches themselves")
         if token_rows is None:  # unset: the host plan sizes every batch exactly, the device plan cannot
             token_rows = "fixed" if plan == "device" and mode == "pack" else "exact"
         check_token_options(mode, pack_order, token_rows, handoff)
@@ -73,6 +93,11 @@ class ResidentTokenLoader(ResidentCorpusLoader, HostPlannedTokenLoader):
                          token_rows=token_rows, pad_id=pad_id, depth=depth, device=device, n_epochs=n_epochs,
                          resume_state=resume_state, handoff=handoff, labels=labels, ignore_index=ignore_index)
         lay = self.layout
+        self.max_rows = None if max_rows is None else int(max_rows)
+        self._rows = lay.max_segments if max_rows is None else int(max_rows)  # the device pack plan's static rows
+        self._ffd = ffd_device
+        if ffd_device:
+            self.pack_order = "ffd_device"
         if plan == "device" and self.LB * source.max_len > 0x7FFFFFFF:  # the host plan checks every batch instead
             raise ValueError(f"{self.LB} sequences of up to {source.max_len} tokens in one batch can overflow int32 "
                              "cu_seqlens")
@@ -96,8 +121,8 @@ class ResidentTokenLoader(ResidentCorpusLoader, HostPlannedTokenLoader):
             return
         self._replica.offsets(self._offs_t, self.prep_stream)
         segs = lay.max_segments if pack else None
-        self._plan_bytes = device_plan_bytes(self.LB, segs, lay.max_segments if pack else 0)
-        self._batch_bytes = device_batch_bytes(lay.max_segments if pack else self.LB, self.seq_len, segs,
+        self._plan_bytes = device_plan_bytes(self.LB, segs, self._rows if pack else 0, ffd=self._ffd)
+        self._batch_bytes = device_batch_bytes(self._rows if pack else self.LB, self.seq_len, segs,
                                                labels=self.labels)
         self._windows = [torch.empty(self._plan_bytes, dtype=torch.uint8, device=self.device)
                          for _ in range(self.depth + 1)]
@@ -113,8 +138,9 @@ class ResidentTokenLoader(ResidentCorpusLoader, HostPlannedTokenLoader):
             kw = dict(perm=self._perm(e), base=base, count=LB, seq_len=S, pad_id=self.pad_id, labels=self.labels,
                       ignore_index=self.ignore_index)
             if pack:
-                r = pack_tokens_indexed_device(self._toks, self._offs_t, max_rows=lay.max_segments,
-                                               max_segs=lay.max_segments, **kw)
+                r = pack_tokens_indexed_device(self._toks, self._offs_t, max_rows=self._rows,
+                                               max_segs=lay.max_segments,
+                                               pack_order="ffd" if self._ffd else "in_order", **kw)
             else:
                 r = pad_tokens_indexed_device(self._toks, self._offs_t, **kw)
             ev = None
@@ -125,8 +151,8 @@ class ResidentTokenLoader(ResidentCorpusLoader, HostPlannedTokenLoader):
                 tok16=self.source.token_bytes == 2, corpus_offsets_ptr=rep.offsets_dev.data_ptr(),
                 n_corpus=self.source.n, selector=dict(self._selector(e), base=base), n=LB, seq_len=S,
                 pad_id=self.pad_id, pack=pack, max_segs=lay.max_segments if pack else 0,
-                max_rows=lay.max_segments if pack else 0, stream=self.prep_stream.cuda_stream, labels=self.labels,
-                ignore_index=self.ignore_index))
+                max_rows=self._rows if pack else 0, stream=self.prep_stream.cuda_stream, labels=self.labels,
+                ignore_index=self.ignore_index, ffd=self._ffd))
         counts = r.pop("counts")
         r["n_tokens"] = counts[2]
         if pack:
@@ -198,6 +224,8 @@ class ResidentTokenLoader(ResidentCorpusLoader, HostPlannedTokenLoader):
                "handoff": self.handoff, "host_waits": self.host_waits, "replica_shared": self.replica_shared}
         if self.plan != "host":  # the default mode's stats stay exactly as they were
             out["plan"] = self.plan
+        if self._ffd:
+            out["pack_order"] = self.pack_order
         return out
 
     def close(self) -> None:

@@ -30,7 +30,9 @@ checkpoint. ``DDL_DEVICE=cpu`` runs it (and ``--zero-copy``) with the host twin.
 
 ``--resident --device-plan`` also builds each batch's order and pack plan on the GPU (``plan="device"``): the host
 only issues launches. Packing is in-order, shapes are static (fixed rows, ``cu_seqlens`` of fixed capacity) and
-``n_tokens`` / ``n_rows`` / ``n_seg`` are 0-d device tensors; ``max_seqlen`` is an upper bound.
+``n_tokens`` / ``n_rows`` / ``n_seg`` are 0-d device tensors; ``max_seqlen`` is an upper bound. ``--ffd`` adds the
+first-fit-decreasing order to that mode (``pack_order="ffd_device"``: one more kernel, the batches of the host FFD
+plan, at most 4096 sequences per rank and step).
 
 ``--resident --stream`` delivers the GPT pre-training format instead (``ResidentTokenStreamLoader``): the epoch's
 shuffled documents concatenated and cut every ``seq_len`` tokens, so ``--global-batch`` counts ROWS, every row is
@@ -79,6 +81,9 @@ def main() -> None:
     ap.add_argument("--device-plan", action="store_true",
                     help="with --resident: the batch's order and pack plan are built on the GPU too (in-order "
                          "packing, static shapes, counts as device scalars)")
+    ap.add_argument("--ffd", action="store_true",
+                    help="with --resident --device-plan --mode pack: first-fit-decreasing rows, ordered by a kernel "
+                         "(pack_order='ffd_device')")
     ap.add_argument("--stream", action="store_true",
                     help="with --resident or --zero-copy: full rows cut from the concatenated shuffled documents "
                          "(--global-batch counts rows)")
@@ -97,6 +102,8 @@ def main() -> None:
         ap.error("--zero-copy and --resident are two loaders: pick one")
     if a.device_plan and not a.resident:
         ap.error("--device-plan is a mode of --resident")
+    if a.ffd and (not a.device_plan or a.mode != "pack"):
+        ap.error("--ffd is an option of --resident --device-plan --mode pack")
     if a.stream and (not (a.resident or a.zero_copy) or a.device_plan or a.mode != "pack"):
         ap.error("--stream is a format of --resident and --zero-copy (packed rows by construction; it has no "
                  "--device-plan mode)")
@@ -135,9 +142,10 @@ def main() -> None:
                 if mix is not None and env.rank == 0:
                     print(f"mix: {mix.parts} parts x {list(mix.repeat)} -> {mix.n_order} documents and "
                           f"{dl.total_tokens} tokens per epoch (the corpus: {a.n_seqs} documents)", flush=True)
-            elif a.resident and a.device_plan:  # first-fit-decreasing is a host plan
+            elif a.resident and a.device_plan:  # in-order, or first-fit-decreasing built by a kernel
                 dl = ddl_amd.ResidentTokenLoader(src, a.global_batch, a.seq_len, a.mode, env, n_epochs=a.epochs,
-                                                 plan="device", **lab_kw)
+                                                 plan="device", pack_order="ffd_device" if a.ffd else "in_order",
+                                                 **lab_kw)
             elif a.resident:
                 dl = ddl_amd.ResidentTokenLoader(src, a.global_batch, a.seq_len, a.mode, env, pack_order=pack_order,
                                                  n_epochs=a.epochs, **lab_kw)
