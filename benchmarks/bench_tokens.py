@@ -17,6 +17,83 @@ import time
 import numpy as np
 
 
+def _fim_report(a, stream_loader, fim, dev):
+    """``--fim``: the stream loader without and with FIM in turns (fresh loaders, this rank's batches: real tokens per
+    second of wall time behind a device synchronise, and the mean device time of a step's launches), and the
+    ``token_fim`` kernel alone between device events on one rendered batch, next to a device copy of as many bytes as
+    the kernel reads and writes (4 B ids, 4 B segment ids and 8 B position ids read, 4 B ids and, with labels, 8 B
+    written per position)."""
+    import torch
+
+    from ddl_amd import _native
+    from ddl_amd.ops.kernels import launch_fim
+
+    runs = []
+    for turn in range(4):
+        dl = stream_loader(fim if turn % 2 else None)
+
+        def gen():
+            while True:
+                yield from dl
+
+        it = gen()
+        for _ in range(a.warmup):
+            next(it)
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
+        real = torch.zeros((), dtype=torch.int64, device=dev)
+        for _ in range(a.steps):
+            real.add_(next(it)["n_tokens"])
+        torch.cuda.synchronize(dev)
+        dt = time.perf_counter() - t0
+        timing = dl.timing()
+        runs.append({"fim": bool(turn % 2), "tokens_per_s": round(int(real) / dt, 1),
+                     "ms_per_step": round(1e3 * dt / a.steps, 4),
+                     "kernel_us": None if timing["kernel_us"] is None else round(timing["kernel_us"], 1),
+                     "kernel_samples": timing["kernel_samples"]})
+        if turn == 3:  # the kernel alone, on the last delivered batch of the FIM loader's plain twin
+            dl.close()
+            dl = stream_loader(None)
+            b = next(iter(dl))
+            R, S = b["input_ids"].shape
+            keys = torch.arange(b["cu_seqlens"].numel() - 1, dtype=torch.int64, device=dev) * 977
+            out = torch.empty((R, S), dtype=torch.int32, device=dev)
+            lab = torch.empty((R, S), dtype=torch.int64, device=dev) if a.labels else None
+            moved = R * S * (4 + 4 + b["position_ids"].element_size() + 4 + (8 if a.labels else 0))
+            src_buf = torch.empty(moved // 2, dtype=torch.uint8, device=dev)
+            dst_buf = torch.empty_like(src_buf)
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            h = _native.hip()
+
+            def fim_launch():
+                launch_fim(h, ids_ptr=b["input_ids"].data_ptr(), seg=b["segment_ids"], pos=b["position_ids"],
+                           cu_ptr=b["cu_seqlens"].data_ptr(), cap=keys.numel(), seg_keys_ptr=keys.data_ptr(),
+                           counts_ptr=0, out_ptr=out.data_ptr(), labels_ptr=lab.data_ptr() if a.labels else 0,
+                           ignore_index=-100, rows=R, seq_len=S, fim_args=fim.device_args(0, 0), stream=stream)
+
+            def timed(fn, n=200):
+                for _ in range(20):
+                    fn()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(n):
+                    fn()
+                e1.record()
+                torch.cuda.synchronize(dev)
+                return 1e3 * e0.elapsed_time(e1) / n
+
+            torch.cuda.synchronize(dev)
+            k_us = [timed(fim_launch), timed(lambda: dst_buf.copy_(src_buf)), timed(fim_launch),
+                    timed(lambda: dst_buf.copy_(src_buf))]
+            kernel = {"rows": R, "seq_len": S, "labels": bool(a.labels), "bytes_moved": moved,
+                      "token_fim_us": [round(k_us[0], 2), round(k_us[2], 2)],
+                      "copy_same_bytes_us": [round(k_us[1], 2), round(k_us[3], 2)],
+                      "token_fim_tbps": round(moved / min(k_us[0], k_us[2]) / 1e6, 3),
+                      "copy_tbps": round(moved / min(k_us[1], k_us[3]) / 1e6, 3)}
+        dl.close()
+    return {"rate": a.fim, "runs": runs, "kernel": kernel}
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=1000)
@@ -70,6 +147,10 @@ def main(argv=None):
     ap.add_argument("--mix", default=None, metavar="R0,R1,...",
                     help="with --stream: repeats of equal parts of the corpus, e.g. 2,1,0.5 (TokenMix: the epoch's "
                          "document order is written by token_mix_order and read as an explicit index)")
+    ap.add_argument("--fim", type=float, default=None, metavar="RATE",
+                    help="with --stream: that share of the segments rearranged for fill-in-the-middle (TokenFIM, one "
+                         "more launch per step); also reports, from the same job, the loader without it, run in turns "
+                         "with it, and the token_fim kernel alone against a copy of the bytes it moves")
     ap.add_argument("--max-blocks", type=int, default=None,
                     help="zerocopy: grid cap of the gather kernel (0 = uncapped; default: the loader's)")
     ap.add_argument("--labels", action="store_true",
@@ -88,6 +169,8 @@ def main(argv=None):
         ap.error("--shuffle-rows needs --stream")
     if a.mix and not a.stream:
         ap.error("--mix needs --stream")
+    if a.fim is not None and not a.stream:
+        ap.error("--fim needs --stream")
     if a.plan == "device" and a.mode == "pack":
         if a.pack_order == "ffd":
             ap.error("--plan device builds the in-order plan (--pack-order in_order) or, with one more kernel, the "
@@ -142,14 +225,21 @@ def main(argv=None):
                 if a.mix:  # equal parts of the corpus, by document index
                     repeat = [float(r) for r in a.mix.split(",")]
                     mix = ddl_amd.TokenMix([round(p * a.n_seqs / len(repeat)) for p in range(len(repeat) + 1)], repeat)
-                if resident:
-                    dl = ddl_amd.ResidentTokenStreamLoader(source, gb, a.seq_len, env, labels=a.labels,
-                                                           shuffle_rows=a.shuffle_rows, mix=mix)
-                else:
-                    dl = ddl_amd.ZeroCopyTokenStreamLoader(source, gb, a.seq_len, env, labels=a.labels,
-                                                           shuffle_rows=a.shuffle_rows, mix=mix,
-                                                           max_blocks=a.max_blocks)
-                dl.profile_every = a.kernel_sample
+                fim = None
+                if a.fim is not None:  # the sentinels past every id of the (at most 16-bit) synthetic vocabulary
+                    fim = ddl_amd.TokenFIM(a.fim, prefix_id=65536, middle_id=65537, suffix_id=65538)
+
+                def stream_loader(fim):
+                    kw = dict(labels=a.labels, shuffle_rows=a.shuffle_rows, mix=mix, fim=fim)
+                    if resident:
+                        dl = ddl_amd.ResidentTokenStreamLoader(source, gb, a.seq_len, env, **kw)
+                    else:
+                        dl = ddl_amd.ZeroCopyTokenStreamLoader(source, gb, a.seq_len, env, max_blocks=a.max_blocks,
+                                                               **kw)
+                    dl.profile_every = a.kernel_sample
+                    return dl
+
+                dl = stream_loader(fim)
             elif resident:
                 dl = ddl_amd.ResidentTokenLoader(source, gb, a.seq_len, a.mode, env, pack_order=pack_order,
                                                  token_rows=a.token_rows, n_epochs=n_epochs, plan=a.plan,
@@ -274,6 +364,9 @@ def main(argv=None):
                 dist.all_reduce(t, group=env.control_group)
                 delivered = float(t.item())
             dl.close()
+            fim_report = None
+            if a.stream and a.fim is not None and dev.type == "cuda":
+                fim_report = _fim_report(a, stream_loader, fim, dev)
             if env.rank == 0:
                 if resident:
                     per_path = {"path": "resident", "handoff": st["handoff"], "host_waits": st["host_waits"],
@@ -337,7 +430,7 @@ def main(argv=None):
                     "mean_len": round(mean_len, 1),
                     "token_wire_dtype": "uint16" if source.token_bytes == 2 else "int32",
                     "h2d_token_gbps": round(real_tokens * source.token_bytes / dt / 1e9, 2),
-                    **per_path,
+                    **per_path, **({"fim": fim_report} if fim_report is not None else {}),
                     "gpu_idle_pct": None if idle is None else round(idle["gpu_idle_pct"], 3),
                     "train_step": None if idle is None else {
                         "model": f"TokenMLP dim={a.model_dim} depth={a.model_depth} fwd+bwd+SGD bf16",

@@ -924,6 +924,39 @@ PYBIND11_MODULE(_ddl_hip, m) {
       py::arg("n_corpus"), py::arg("cbase"), py::arg("doc_lo"), py::arg("n_docs"), py::arg("full_span"),
       py::arg("inner_shuffle"), py::arg("inner_keys"), py::arg("inner_half_bits"), py::arg("n"), py::arg("order"),
       py::arg("stream"));
+  m.def(
+      "token_fim",
+      [](uintptr_t ids, uintptr_t seg, bool seg_is_i64, uintptr_t pos, bool pos_is_i64, uintptr_t cu, int64_t cap,
+         uintptr_t seg_keys, uintptr_t counts, uintptr_t out, uintptr_t labels, int64_t ignore_index, int64_t rows,
+         int64_t seq_len, uint64_t ekey, uint32_t rate_q, uint32_t spm_q, int32_t prefix_id, int32_t middle_id,
+         int32_t suffix_id, bool has_eod, int32_t eod_id, int32_t min_len, uintptr_t stream) {
+        if (rows < 1 || seq_len < 1 || rows > 0x7FFFFFFF / seq_len)
+          throw std::invalid_argument("token_fim: rows and seq_len must be >= 1 and rows * seq_len fit int32");
+        if (ignore_index < INT32_MIN || ignore_index > INT32_MAX)
+          throw std::invalid_argument("token_fim: ignore_index does not fit int32");
+        ddl::TokenFimSpec sp{};
+        sp.fp = ddl::FimParams{ekey, rate_q, spm_q, prefix_id, middle_id, suffix_id, eod_id, has_eod ? 1 : 0, min_len};
+        sp.ids = as_ptr<const int32_t>(ids);
+        sp.seg = as_ptr<const void>(seg);
+        sp.pos = as_ptr<const void>(pos);
+        sp.seg_is_i64 = seg_is_i64 ? 1 : 0;
+        sp.pos_is_i64 = pos_is_i64 ? 1 : 0;
+        sp.cu = as_ptr<const int32_t>(cu);
+        sp.cap = cap;
+        sp.seg_keys = as_ptr<const int64_t>(seg_keys);
+        sp.counts = as_ptr<const int64_t>(counts);
+        sp.out = as_ptr<int32_t>(out);
+        sp.labels = as_ptr<int64_t>(labels);
+        sp.ignore_index = static_cast<int32_t>(ignore_index);
+        sp.rows = rows;
+        sp.seq_len = seq_len;
+        check_rc(ddl::token_fim(sp, as_stream(stream)), "token_fim");
+      },
+      py::arg("ids"), py::arg("seg"), py::arg("seg_is_i64"), py::arg("pos"), py::arg("pos_is_i64"), py::arg("cu"),
+      py::arg("cap"), py::arg("seg_keys"), py::arg("counts"), py::arg("out"), py::arg("labels"),
+      py::arg("ignore_index"), py::arg("rows"), py::arg("seq_len"), py::arg("ekey"), py::arg("rate_q"),
+      py::arg("spm_q"), py::arg("prefix_id"), py::arg("middle_id"), py::arg("suffix_id"), py::arg("has_eod"),
+      py::arg("eod_id"), py::arg("min_len"), py::arg("stream"));
   m.attr("MIX_MAX_PARTS") = ddl::kMixMaxParts;
   m.attr("TOKEN_SEG_LDS_CAP") = ddl::kTiSegCap;
   m.attr("RAGGED_MAP_CAP") = ddl::kRaggedMapCap;

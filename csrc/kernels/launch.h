@@ -7,6 +7,7 @@
 #include <stdint.h>
 
 #include "common.h"
+#include "tokens_fim.h"
 #include "tokens_mix.h"
 
 namespace ddl {
@@ -292,6 +293,33 @@ struct MixOrderSpec {
   int64_t* order;  // out: [n], device
 };
 int token_mix_order(const MixOrderSpec& spec, hipStream_t st);
+
+// tokens_fim.hip ------------------------------------------------------------
+// Fill-in-the-middle rearrangement of a rendered token batch (tokens_fim.h has the definition): every sound segment
+// of ids [rows, seq_len] whose draw selects it is written rearranged into out, every other position is copied;
+// labels (null: none) are the next-token labels of out. seg / pos: the batch's segment and position ids, int32 or
+// int64; cu [cap + 1]: cu_seqlens; seg_keys [cap]; counts (null: none): counts[0] < 0 marks a batch that is not
+// rearranged. One workgroup per (row, chunk of 512 positions), 4 positions per lane. out and labels must not
+// overlap the inputs; with seq_len a multiple of 4, ids, seg, pos, out and labels must be 16-byte aligned.
+struct TokenFimSpec {
+  FimParams fp;
+  const int32_t* ids;
+  const void* seg;
+  const void* pos;
+  int32_t seg_is_i64;
+  int32_t pos_is_i64;
+  const int32_t* cu;
+  int64_t cap;
+  const int64_t* seg_keys;
+  const int64_t* counts;
+  int32_t* out;
+  int64_t* labels;
+  int32_t ignore_index;
+  int32_t pad;
+  int64_t rows;
+  int64_t seq_len;
+};
+int token_fim(const TokenFimSpec& spec, hipStream_t st);
 
 // ragged.hip ----------------------------------------------------------------
 // Device twin of the host gather_ragged: sequence i (src_start[i] elements into src, dst_offsets[i + 1] -

@@ -24,6 +24,7 @@ __all__ = [
     "ResidentTokenStreamLoader",
     "ZeroCopyTokenStreamLoader",
     "TokenMix",
+    "TokenFIM",
     "DataLoader",
     "OutputSpec",
     "StagingSpec",
@@ -38,6 +39,7 @@ from .datasetwrapper import ProducerFunctionSkeleton
 from .parallel.launcher import distributed_dataloader, start
 from .permutation import EpochOrder, FeistelPermutation
 from .specs import OrderSpec, OutputSpec, StagingSpec
+from .token_fim import TokenFIM
 from .token_mix import TokenMix
 from .types import DDLEnv, Marker
 

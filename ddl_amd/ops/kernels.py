@@ -24,7 +24,7 @@ import numpy as np
 import torch
 
 from .. import _native
-from ..permutation import FeistelPermutation
+from ..permutation import FeistelPermutation, _mix64
 from . import _dtypes
 
 
@@ -1648,13 +1648,17 @@ def _stream_plan_layout(plan_ptr: int, rows: int, max_segs: int) -> tuple[int, i
 def _launch_stream_emit(h, whole: torch.Tensor, plan: tuple, *, corpus_ptr: int, corpus_elems: int, tok16: bool,
                         rows: int, seq_len: int, pad_id: int, max_segs: int, position_dtype, stream: int,
                         labels: bool, ignore_index: int, plan_fn, plan_kw: dict, staging_ptr: int = 0,
-                        max_blocks: int = 0) -> dict:
+                        max_blocks: int = 0, fim: dict | None = None) -> dict:
     """``plan_fn(counts=..., **plan_kw)`` and ``pad_pack_tokens_indexed`` over the plan it wrote (pack mode, counts
     read from device memory), with everything returned carved from ``whole``. ``staging_ptr``: the zero-copy form
     (``launch_stream_plan_zerocopy``) -- ``gather_stream_pieces`` between the two copies the batch's tokens from the
-    corpus into that window, which the emit launch then reads as its corpus."""
+    corpus into that window, which the emit launch then reads as its corpus. ``fim`` (``scratch_ptr``: ``rows *
+    seq_len`` int32 of 16-byte aligned device memory, ``args``: ``TokenFIM.device_args`` of the epoch): the emit
+    launch renders its ids there and writes no labels, and ``token_fim`` -- one more launch behind it -- writes the
+    batch's ``input_ids`` and ``labels``, keyed by the plan's ``seg_src``."""
     S, R, M = int(seq_len), int(rows), int(max_segs)
     o_ss, o_so, o_rs, o_re, _ = plan
+    o_keys = o_ss
     out_b = token_output_bytes(R, S, M, position_dtype, labels)
     ids, mask, pos, seg, cu, *lab = carve_token_outputs(whole, R, S, M, position_dtype, labels)
     counts = whole[out_b:out_b + 32].view(torch.int64)
@@ -1669,11 +1673,15 @@ def _launch_stream_emit(h, whole: torch.Tensor, plan: tuple, *, corpus_ptr: int,
         corpus_ptr, corpus_elems, o_ss = staging_ptr, R * S, o_so
     h.pad_pack_tokens_indexed(
         corpus=corpus_ptr, corpus_elems=corpus_elems, src_start=0, seg_src=o_ss, offsets=0, row_start=o_rs,
-        row_end=o_re, seg_offsets=o_so, n_seg=0, out_tokens=ids.data_ptr(), attn_mask=mask.data_ptr(),
-        position_ids=pos.data_ptr(), pos_is_i64=position_dtype == torch.int64, segment_ids=seg.data_ptr(),
-        cu_seqlens_out=cu.data_ptr(), rows=0, seq_len=S, pad_id=pad_id, mode=1, stream=stream, fill_rows=R,
-        tok16=tok16, dev_counts=c_ptr, cu_cap=M, labels=lab[0].data_ptr() if labels else 0,
-        ignore_index=ignore_index)
+        row_end=o_re, seg_offsets=o_so, n_seg=0, out_tokens=fim["scratch_ptr"] if fim else ids.data_ptr(),
+        attn_mask=mask.data_ptr(), position_ids=pos.data_ptr(), pos_is_i64=position_dtype == torch.int64,
+        segment_ids=seg.data_ptr(), cu_seqlens_out=cu.data_ptr(), rows=0, seq_len=S, pad_id=pad_id, mode=1,
+        stream=stream, fill_rows=R, tok16=tok16, dev_counts=c_ptr, cu_cap=M,
+        labels=lab[0].data_ptr() if labels and not fim else 0, ignore_index=ignore_index)
+    if fim:
+        launch_fim(h, ids_ptr=fim["scratch_ptr"], seg=seg, pos=pos, cu_ptr=cu.data_ptr(), cap=M, seg_keys_ptr=o_keys,
+                   counts_ptr=c_ptr, out_ptr=ids.data_ptr(), labels_ptr=lab[0].data_ptr() if labels else 0,
+                   ignore_index=ignore_index, rows=R, seq_len=S, fim_args=fim["args"], stream=stream)
     r = {"input_ids": ids, "attention_mask": mask, "position_ids": pos, "segment_ids": seg, "cu_seqlens": cu,
          "counts": counts}
     if labels:
@@ -1685,13 +1693,15 @@ def launch_stream_plan(plan_ptr: int, whole: torch.Tensor, *, corpus_ptr: int, c
                        corpus_offsets_ptr: int, n_corpus: int, table_ptr: int, selector: dict, row_base: int,
                        rows: int, seq_len: int, pad_id: int, max_segs: int, position_dtype=torch.int64,
                        stream: int = 0, labels: bool = False, ignore_index: int = -100,
-                       n: int | None = None, staging_ptr: int = 0, max_blocks: int = 0) -> dict:
+                       n: int | None = None, staging_ptr: int = 0, max_blocks: int = 0,
+                       fim: dict | None = None) -> dict:
     """The two launches of one token stream batch on raw stream ``stream``: ``token_stream_plan`` and
     ``pad_pack_tokens_indexed`` (pack mode, counts read from device memory). ``plan_ptr`` / ``whole``: the two
     sizes of ``token_stream_bytes``, 16-byte aligned device memory; ``selector``: the ``RowIndex`` of the epoch's
     order with base 0, the one ``table_ptr``'s table was built with; ``n``: the order's length where it is not the
     corpus's document count (an explicit order). Nothing here allocates, copies or synchronises. Returns the dict of
-    ``stream_tokens_indexed_device``. ``staging_ptr`` / ``max_blocks``: ``launch_stream_plan_zerocopy``'s."""
+    ``stream_tokens_indexed_device``. ``staging_ptr`` / ``max_blocks``: ``launch_stream_plan_zerocopy``'s; ``fim``:
+    ``_launch_stream_emit``'s, a third launch."""
     h = _native.hip()
     S, R, M = int(seq_len), int(rows), int(max_segs)
     ignore_index = check_ignore_index(labels, ignore_index)
@@ -1703,7 +1713,7 @@ def launch_stream_plan(plan_ptr: int, whole: torch.Tensor, *, corpus_ptr: int, c
     return _launch_stream_emit(h, whole, plan, corpus_ptr=corpus_ptr, corpus_elems=corpus_elems, tok16=tok16, rows=R,
                                seq_len=S, pad_id=pad_id, max_segs=M, position_dtype=position_dtype, stream=stream,
                                labels=labels, ignore_index=ignore_index, plan_fn=h.token_stream_plan, plan_kw=plan_kw,
-                               staging_ptr=staging_ptr, max_blocks=max_blocks)
+                               staging_ptr=staging_ptr, max_blocks=max_blocks, fim=fim)
 
 
 def launch_stream_plan_rows(plan_ptr: int, whole: torch.Tensor, *, corpus_ptr: int, corpus_elems: int, tok16: bool,
@@ -1711,7 +1721,7 @@ def launch_stream_plan_rows(plan_ptr: int, whole: torch.Tensor, *, corpus_ptr: i
                             row_selector: dict, stream_rows: int, rows: int, seq_len: int, pad_id: int,
                             max_segs: int, position_dtype=torch.int64, stream: int = 0, labels: bool = False,
                             ignore_index: int = -100, n: int | None = None, staging_ptr: int = 0,
-                            max_blocks: int = 0) -> dict:
+                            max_blocks: int = 0, fim: dict | None = None) -> dict:
     """``launch_stream_plan`` for rows picked anywhere in the stream: the two launches of ``token_stream_plan_rows``
     and ``pad_pack_tokens_indexed``, the call it is for contiguous rows. ``plan_ptr``: the plan size of
     ``token_stream_bytes(..., shuffled_rows=True)``; ``row_selector``: the ``RowIndex`` arguments that select the
@@ -1730,7 +1740,7 @@ def launch_stream_plan_rows(plan_ptr: int, whole: torch.Tensor, *, corpus_ptr: i
     return _launch_stream_emit(h, whole, plan, corpus_ptr=corpus_ptr, corpus_elems=corpus_elems, tok16=tok16, rows=R,
                                seq_len=S, pad_id=pad_id, max_segs=M, position_dtype=position_dtype, stream=stream,
                                labels=labels, ignore_index=ignore_index, plan_fn=h.token_stream_plan_rows,
-                               plan_kw=plan_kw, staging_ptr=staging_ptr, max_blocks=max_blocks)
+                               plan_kw=plan_kw, staging_ptr=staging_ptr, max_blocks=max_blocks, fim=fim)
 
 
 def stream_staging_bytes(rows: int, seq_len: int, token_bytes: int) -> int:
@@ -1998,6 +2008,198 @@ def launch_mix_order(h, order_ptr: int, parts: dict, *, n_corpus: int, n: int, p
     not change with the epoch), ``perm`` = the epoch's permutation of the ``n`` entries or None."""
     h.token_mix_order(n_corpus=int(n_corpus), n=int(n), order=order_ptr, stream=stream, **parts,
                       **_index_kw(None, perm, 0))
+
+
+# ------------------------------------------- fill-in-the-middle rearrangement of a rendered token batch
+def _stream_seg_keys(corpus_offsets, batch: dict, *, perm=None, order=None, row_base: int, seq_len: int,
+                        row_perm: FeistelPermutation | None = None, row_index=None) -> np.ndarray:
+    """``seg_keys`` (int64 [n_seg]) of a ``ref_stream_tokens`` batch of the same arguments, as the stream plans write
+    them (``seg_src``): the corpus element of each segment's first token. From the batch's own segments: segment
+    ``s`` starts at batch position ``cu_seqlens[s]``, stream position ``g``, inside the order's document ``d``, at
+    corpus element ``offs[q_d] + g - table[d]``. An overflowed or invalid batch has none."""
+    S = int(seq_len)
+    counts = batch["counts"].tolist()
+    if counts[0] < 0:
+        return np.zeros(0, dtype=np.int64)
+    n_seg = int(counts[1])
+    offs = torch.as_tensor(corpus_offsets).to("cpu", torch.int64).reshape(-1).numpy()
+    q = _host_order(order, perm)
+    if q is None:
+        q = _stream_order(offs.size - 1, perm)
+        lens = _stream_lengths(offs, q)
+    else:
+        lens = _order_lengths(offs, q)
+    table = np.concatenate([np.zeros(1, dtype=np.int64), np.cumsum(lens, dtype=np.int64)])
+    at = batch["cu_seqlens"].numpy()[:n_seg].astype(np.int64)
+    rows = int(batch["input_ids"].shape[0])
+    rho = _stream_row_select(row_perm, row_index, int(row_base), rows)
+    k = at // S
+    g = (int(row_base) + k if rho is None else rho[k]) * S + at % S
+    d = np.searchsorted(table, g, side="right") - 1
+    return offs[q[d]] + (g - table[d])
+
+
+def _fim_n_rows(batch: dict):
+    """The entry of a batch dict that holds ``n_rows`` (``counts`` of the ops, ``n_rows`` of the loaders), or None."""
+    if "counts" in batch:
+        return batch["counts"].reshape(-1)[:1]
+    return batch.get("n_rows")
+
+
+def _fim_check_batch(batch: dict, fim, labels: bool):
+    from ..token_fim import TokenFIM
+
+    if not isinstance(fim, TokenFIM):
+        raise TypeError("fim must be a TokenFIM")
+    for key in ("input_ids", "segment_ids", "position_ids", "cu_seqlens") + (("attention_mask",) if labels else ()):
+        if not isinstance(batch.get(key), torch.Tensor):
+            raise ValueError(f"fim_tokens: the batch has no tensor {key!r} (a batch of the pack or stream ops)")
+    ids, seg, pos, cu = batch["input_ids"], batch["segment_ids"], batch["position_ids"], batch["cu_seqlens"]
+    if ids.dtype != torch.int32 or ids.dim() != 2 or cu.dtype != torch.int32 or cu.dim() != 1 or cu.numel() < 1:
+        raise TypeError("fim_tokens: input_ids must be int32 [R, S] and cu_seqlens int32 [capacity + 1]")
+    for name, t in (("segment_ids", seg), ("position_ids", pos)):
+        if t.dtype not in (torch.int32, torch.int64) or t.shape != ids.shape:
+            raise TypeError(f"fim_tokens: {name} must be int32 or int64 of input_ids' shape")
+    R, S = int(ids.shape[0]), int(ids.shape[1])
+    if R < 1 or S < 1 or R * S > 0x7FFFFFFF:
+        raise ValueError("fim_tokens: rows and seq_len must be >= 1 and rows * seq_len fit int32")
+    return ids, seg, pos, cu, R, S
+
+
+def ref_fim_tokens(batch: dict, fim, *, seg_keys, seed: int, epoch: int, labels: bool = False,
+                   ignore_index: int = -100) -> dict:
+    """The definition of the fill-in-the-middle rearrangement (``token_fim.TokenFIM`` has the arithmetic), in NumPy on
+    the CPU. ``batch``: a dict of the pack or stream ops (``input_ids`` int32 [R, S], ``segment_ids``,
+    ``position_ids``, ``cu_seqlens``; ``attention_mask`` for labels); ``seg_keys``: int64, the key of every segment
+    (at least as many as the batch has segments; the loaders: the plan's ``seg_src``). A position belongs to segment
+    ``s = segment_ids``, at offset ``j = position_ids`` of its ``L = cu_seqlens[s + 1] - cu_seqlens[s]`` tokens, which
+    lie at columns ``[col - j, col - j + L)`` of its row; a position that is not part of such a segment (padding, ``s``
+    outside the capacity or the keys, a run that leaves the row: none in a batch the ops rendered, given a key for
+    every segment) keeps its token and has no target. Returns a new dict: ``input_ids`` is a new tensor, ``labels``
+    (with ``labels=True``) are ``ref_token_labels`` of it -- labels of the input are dropped without --, every other
+    entry is the input's. A batch with ``n_rows`` < 0 (``counts`` or ``n_rows`` of
+    the dict: overflowed or invalid) is not rearranged."""
+    ids_t, seg_t, pos_t, cu_t, R, S = _fim_check_batch(batch, fim, labels)
+    ignore_index = check_ignore_index(labels, ignore_index)
+    ids = ids_t.cpu().numpy()
+    sid = seg_t.cpu().numpy().astype(np.int64)
+    pos = pos_t.cpu().numpy().astype(np.int64)
+    cu = cu_t.cpu().numpy().astype(np.int64)
+    keys = (seg_keys.detach().cpu().numpy() if isinstance(seg_keys, torch.Tensor) else np.asarray(seg_keys))
+    if keys.dtype != np.int64:
+        raise TypeError("seg_keys must be int64")
+    keys = keys.reshape(-1)
+    cap = min(cu.size - 1, keys.size)
+    n_rows = _fim_n_rows(batch)
+    live = n_rows is None or int(torch.as_tensor(n_rows).reshape(-1)[0]) >= 0
+    out = ids.copy()
+    sound = (sid >= 0) & (sid < cap)
+    if cap > 0:
+        s = np.where(sound, sid, 0)
+        L = cu[s + 1] - cu[s]
+        col = np.broadcast_to(np.arange(S, dtype=np.int64), (R, S))
+        row = np.broadcast_to(np.arange(R, dtype=np.int64)[:, None], (R, S))
+        sound &= (pos >= 0) & (pos <= col)
+        c0 = np.where(sound, col - pos, 0)  # the segment's first column
+        sound &= (L >= 1) & (pos < L) & (c0 <= S - L)
+    if live and sound.any():
+        c0 = np.where(sound, c0, 0)
+        L = np.where(sound, L, 1)
+        tail = np.zeros((R, S), dtype=np.int64)
+        if fim.eod_id is not None:
+            tail = (ids[row, c0 + L - 1] == fim.eod_id).astype(np.int64)
+        M = L - tail
+        K = M - 3
+        k4 = keys[s].astype(np.uint64) << np.uint64(2)
+        ekey = np.uint64(fim.epoch_key(seed, epoch))
+        u = [_mix64(ekey ^ _mix64(k4 + np.uint64(c))) for c in range(4)]
+        sel = sound & (M >= fim.min_len) & ((u[0] >> np.uint64(40)) < np.uint64(fim.rate_q))
+        spm = (u[1] >> np.uint64(40)) < np.uint64(fim.spm_q)
+        K1 = np.where(sel, K + 1, 1).astype(np.uint64)
+        x = (((u[2] >> np.uint64(32)) * K1) >> np.uint64(32)).astype(np.int64)
+        y = (((u[3] >> np.uint64(32)) * K1) >> np.uint64(32)).astype(np.int64)
+        a, b = np.minimum(x, y), np.maximum(x, y)
+        n_suf = K - b
+        j = pos
+        PRE, SUF, MID = -1, -2, -3
+        psm = np.select(
+            [j == 0, j <= a, j == a + 1, j < a + 2 + n_suf, j == a + 2 + n_suf],
+            [PRE, j - 1, SUF, b + (j - (a + 2)), MID], a + (j - (a + 3 + n_suf)))
+        spm_src = np.select(
+            [j == 0, j == 1, j < 2 + n_suf, j == 2 + n_suf],
+            [PRE, SUF, b + (j - 2), MID], j - (3 + n_suf))
+        src = np.where(spm, spm_src, psm)
+        src = np.where(sel & (j < K + 3), src, j)  # untouched segments, and the EOD that stays last
+        moved = sel & (src >= 0)
+        gathered = ids[row, np.where(moved, c0 + src, 0)]
+        out = np.where(moved, gathered, out)
+        for code, tok in ((PRE, fim.prefix_id), (SUF, fim.suffix_id), (MID, fim.middle_id)):
+            out = np.where(sel & (src == code), np.int32(tok), out)
+        out = np.ascontiguousarray(out, dtype=np.int32)
+    r = dict(batch)
+    r.pop("labels", None)
+    r["input_ids"] = torch.from_numpy(out)
+    if labels:
+        lab = ref_token_labels(r["input_ids"], batch["attention_mask"].cpu(), seg_t.cpu(), ignore_index)
+        lab[torch.from_numpy(~sound)] = ignore_index  # a position outside every sound segment has no target
+        r["labels"] = lab
+    return r
+
+
+def launch_fim(h, *, ids_ptr: int, seg: torch.Tensor, pos: torch.Tensor, cu_ptr: int, cap: int, seg_keys_ptr: int,
+               counts_ptr: int, out_ptr: int, labels_ptr: int, ignore_index: int, rows: int, seq_len: int,
+               fim_args: dict, stream: int) -> None:
+    """The one launch of ``token_fim`` on raw stream ``stream``: ``fim_args`` = ``TokenFIM.device_args(seed, epoch)``;
+    ``seg`` / ``pos`` give their addresses and widths. Nothing here allocates, copies or synchronises."""
+    h.token_fim(ids=ids_ptr, seg=seg.data_ptr(), seg_is_i64=seg.dtype == torch.int64, pos=pos.data_ptr(),
+                pos_is_i64=pos.dtype == torch.int64, cu=cu_ptr, cap=int(cap), seg_keys=seg_keys_ptr,
+                counts=counts_ptr, out=out_ptr, labels=labels_ptr, ignore_index=int(ignore_index), rows=int(rows),
+                seq_len=int(seq_len), stream=stream, **fim_args)
+
+
+def fim_tokens(batch: dict, fim, *, seg_keys, seed: int, epoch: int, labels: bool = False,
+               ignore_index: int = -100, stream=None) -> dict:
+    """``ref_fim_tokens`` (the definition) of a batch on the device by the ``token_fim`` kernel: one launch, one
+    workgroup per (row, 512 positions), no copy and no synchronisation; the new ``input_ids`` and ``labels`` are
+    allocated here. The batch's tensors and ``seg_keys`` (an int64 tensor) must be contiguous and on one GPU; where
+    the dict holds the device ``counts`` (or a device ``n_rows``) the kernel reads ``n_rows`` there. The label of a
+    position is its segment's next rearranged token, which is ``ref_token_labels`` of the new ids for every batch
+    the pack and stream ops render. A batch of CPU tensors takes the reference."""
+    ids, seg, pos, cu, R, S = _fim_check_batch(batch, fim, labels)
+    ignore_index = check_ignore_index(labels, ignore_index)
+    if not ids.is_cuda:
+        return ref_fim_tokens(batch, fim, seg_keys=seg_keys, seed=seed, epoch=epoch, labels=labels,
+                              ignore_index=ignore_index)
+    if not isinstance(seg_keys, torch.Tensor) or seg_keys.dtype != torch.int64:
+        raise TypeError("fim_tokens: seg_keys must be an int64 tensor")
+    n_rows = _fim_n_rows(batch)
+    fim_args = fim.device_args(seed, epoch)
+    if not isinstance(n_rows, torch.Tensor) or not n_rows.is_cuda:
+        if n_rows is not None and int(torch.as_tensor(n_rows).reshape(-1)[0]) < 0:
+            fim_args["rate_q"] = 0  # a host value the caller has read: an invalid batch is copied
+        n_rows = None
+    elif n_rows.dtype != torch.int64:
+        raise TypeError("fim_tokens: counts / n_rows must be int64")
+    dev = ids.device
+    for name, t in (("input_ids", ids), ("segment_ids", seg), ("position_ids", pos), ("cu_seqlens", cu),
+                    ("seg_keys", seg_keys), ("counts", n_rows)):
+        if t is not None and (t.device != dev or not t.is_contiguous()):
+            raise ValueError(f"fim_tokens: {name} must be contiguous and on the batch's GPU")
+    handle, tstream = _stream_pair(stream, dev)
+    with torch.cuda.stream(tstream):
+        out = torch.empty((R, S), dtype=torch.int32, device=dev)
+        lab = torch.empty((R, S), dtype=torch.int64, device=dev) if labels else None
+    launch_fim(_native.hip(), ids_ptr=ids.data_ptr(), seg=seg, pos=pos, cu_ptr=cu.data_ptr(),
+               cap=min(cu.numel() - 1, seg_keys.numel()), seg_keys_ptr=seg_keys.data_ptr(),
+               counts_ptr=0 if n_rows is None else n_rows.data_ptr(), out_ptr=out.data_ptr(),
+               labels_ptr=lab.data_ptr() if labels else 0, ignore_index=ignore_index, rows=R, seq_len=S,
+               fim_args=fim_args, stream=handle)
+    r = dict(batch)
+    r.pop("labels", None)
+    r["input_ids"] = out
+    if labels:
+        r["labels"] = lab
+    return r
 
 
 def _check_row_perm(row_perm: FeistelPermutation, stream_rows: int, row_base: int, rows: int) -> None:

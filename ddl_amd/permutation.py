@@ -81,6 +81,16 @@ def part_seed_for(seed: int, part: int) -> int:
     return _mix64_int(z) & ((1 << 63) - 1)
 
 
+_FIM_SEED_SALT = 0x66696D5F63757473  # "fim_cuts"
+
+
+def fim_seed_for(seed: int) -> int:
+    """The seed of the token stream loaders' fill-in-the-middle draws (``TokenFIM``), derived from the loader's
+    ``seed`` like ``row_seed_for`` with a salt of its own, so that which segments are rearranged and where they are
+    cut is independent of the documents' and the rows' order."""
+    return _mix64_int((int(seed) ^ _FIM_SEED_SALT) & _MASK64) & ((1 << 63) - 1)
+
+
 def half_bits_for(n: int) -> int:
     if n <= 0:
         raise ValueError("permutation domain must be positive")

@@ -43,6 +43,15 @@ order into one of two int64 buffers of ``N'`` entries (next to the two tables, o
 table scan), and the table, plan and emit kernels read it as an explicit index: still no copy, no host read of
 device memory and no synchronisation. The extra documents of a fractional repeat are the same in every epoch
 (``token_mix``), which keeps ``total_tokens``, the rows and batches per epoch and the checkpoint cursor constant.
+
+``fim=TokenFIM(rate, ...)`` rearranges a share of every batch's segments for fill-in-the-middle training
+(``token_fim`` has the definition, ``ops.ref_fim_tokens``): the emit launch renders its ids into a scratch area at
+the end of the step's window and writes no labels, and ``token_fim`` -- one more launch on the prep stream -- writes
+the batch's ``input_ids`` and ``labels``. A segment's key is the plan's ``seg_src``, the corpus element of its first
+token, and the epoch's key follows from ``seed`` and the epoch: the rearrangement does not depend on the world size,
+the rank, ``shuffle_rows``, the batch a row lands in or where the tokens lie. With a ``mix``, two copies of a
+document in one epoch get the same cuts where their pieces start at the same token. Without ``fim`` the launches,
+buffers and bytes are unchanged.
 """
 
 from __future__ import annotations
@@ -54,10 +63,12 @@ from . import _native
 from .corpus_replica import ResidentCorpusLoader
 from .exceptions import DDLError
 from .models.tokens import SharedTokenSource
-from .ops.kernels import (check_ignore_index, launch_mix_order, launch_stream_plan, launch_stream_plan_rows,
-                          ref_mix_order, ref_stream_tokens, row_selector, stream_max_segments, token_stream_bytes)
+from .ops.kernels import (_align16, _stream_seg_keys, check_ignore_index, launch_mix_order, launch_stream_plan,
+                          launch_stream_plan_rows, ref_fim_tokens, ref_mix_order, ref_stream_tokens, row_selector,
+                          stream_max_segments, token_stream_bytes)
 from .permutation import FeistelPermutation, row_seed_for
 from .resident import STATE_VERSION, PrefetchedIndexedLoader
+from .token_fim import TokenFIM
 from .token_mix import TokenMix
 from .types import DDLEnv
 from .utils import streams
@@ -86,12 +97,13 @@ class TokenStreamLoader(ResidentCorpusLoader, PrefetchedIndexedLoader):
         return {}
 
     def _window_bytes(self) -> int:
-        return self._plan_bytes
+        return self._plan_bytes + self._fim_bytes
 
     def _init_stream(self, source: SharedTokenSource, global_batch: int, seq_len: int, env: DDLEnv | None, *,
                      seed: int, shuffle: bool, pad_id: int, depth: int, device, n_epochs: int | None,
                      resume_state: dict | None, handoff: str, max_segments: int | None, labels: bool,
-                     ignore_index: int, shuffle_rows: bool, mix: TokenMix | None) -> None:
+                     ignore_index: int, shuffle_rows: bool, mix: TokenMix | None,
+                     fim: TokenFIM | None = None) -> None:
         """The arguments checked, the epoch's sizes, the cursor and the prep stream: everything in front of the
         corpus itself."""
         if handoff not in ("device", "host"):
@@ -114,6 +126,11 @@ class TokenStreamLoader(ResidentCorpusLoader, PrefetchedIndexedLoader):
         offs = self._offs_t.numpy()
         lens = np.maximum(np.diff(offs), 0)
         self.n_documents, self.total_tokens = int(source.n), int(lens.sum())
+        if fim is not None and not isinstance(fim, TokenFIM):
+            raise TypeError("fim must be a TokenFIM")
+        self.fim = fim
+        # the ids the emit launch renders for token_fim to rearrange: a scratch area at the end of a step's window
+        self._fim_bytes = _align16(4 * self.LB * self.seq_len) if fim is not None else 0
         self.mix = mix
         if mix is not None:
             if not isinstance(mix, TokenMix):
@@ -222,8 +239,14 @@ class TokenStreamLoader(ResidentCorpusLoader, PrefetchedIndexedLoader):
         if st is None:  # the CPU twin: the definition itself
             r = ref_stream_tokens(self._toks, self._offs_t, perm=self._perm(e) if self.mix is None else None,
                                   row_base=row_base, rows=self.LB, seq_len=self.seq_len, pad_id=self.pad_id,
-                                  max_segs=self.max_segments, labels=self.labels, ignore_index=self.ignore_index,
-                                  row_perm=self._row_perm(e), order=self._order(e))
+                                  max_segs=self.max_segments, labels=self.labels and self.fim is None,
+                                  ignore_index=self.ignore_index, row_perm=self._row_perm(e), order=self._order(e))
+            if self.fim is not None:
+                keys = _stream_seg_keys(self._offs_t, r, perm=self._perm(e) if self.mix is None else None,
+                                           order=self._order(e), row_base=row_base, seq_len=self.seq_len,
+                                           row_perm=self._row_perm(e))
+                r = ref_fim_tokens(r, self.fim, seg_keys=keys, seed=self.seed, epoch=e, labels=self.labels,
+                                   ignore_index=self.ignore_index)
             ev = None
         else:
             sel = self._doc_selector(e)
@@ -236,6 +259,9 @@ class TokenStreamLoader(ResidentCorpusLoader, PrefetchedIndexedLoader):
                     n_corpus=self.n_documents, n=self.n_order, table_ptr=table.data_ptr(), selector=sel,
                     rows=self.LB, seq_len=self.seq_len, pad_id=self.pad_id, max_segs=self.max_segments,
                     stream=st.cuda_stream, labels=self.labels, ignore_index=self.ignore_index, **self._launch_kw())
+                if self.fim is not None:
+                    common["fim"] = {"scratch_ptr": win.data_ptr() + self._window_bytes() - self._fim_bytes,
+                                     "args": self.fim.device_args(self.seed, e)}
                 if self.shuffle_rows:
                     return self._launch_plan_rows(
                         win.data_ptr(), whole, stream_rows=self.order.n_samples,
@@ -268,6 +294,7 @@ class TokenStreamLoader(ResidentCorpusLoader, PrefetchedIndexedLoader):
             "world_size": self.W,
             "mix": None if self.mix is None else self.mix.state(),
             "n_order": self.n_order,
+            "fim": None if self.fim is None else self.fim.state(),
         }
 
     def _apply_state(self, sd: dict) -> None:
@@ -277,6 +304,9 @@ class TokenStreamLoader(ResidentCorpusLoader, PrefetchedIndexedLoader):
         mix_state = None if self.mix is None else self.mix.state()
         if sd.get("mix") != mix_state:  # a state without the key: no mix; before total_tokens, which a mix changes
             raise ValueError(f"checkpoint mix={sd.get('mix')} does not match {mix_state}")
+        fim_state = None if self.fim is None else self.fim.state()
+        if sd.get("fim") != fim_state:  # a state without the key: no FIM
+            raise ValueError(f"checkpoint fim={sd.get('fim')} does not match {fim_state}")
         for key, mine in (("global_batch", self.GB), ("seq_len", self.seq_len), ("n_documents", self.n_documents),
                           ("total_tokens", self.total_tokens), ("order_seed", self.seed),
                           ("shuffle", self.order.shuffle), ("n_order", self.n_order)):
@@ -326,7 +356,8 @@ class ResidentTokenStreamLoader(TokenStreamLoader):
                  device: str | torch.device | None = None, n_epochs: int | None = None,
                  resume_state: dict | None = None, handoff: str = "device", hbm_fraction: float = 0.8,
                  chunk_bytes: int = 256 << 20, max_segments: int | None = None, labels: bool = False,
-                 ignore_index: int = -100, shuffle_rows: bool = False, mix: TokenMix | None = None):
+                 ignore_index: int = -100, shuffle_rows: bool = False, mix: TokenMix | None = None,
+                 fim: TokenFIM | None = None):
         """``global_batch`` counts rows. ``max_segments``: the capacity of a batch's ``cu_seqlens`` (default
         ``ops.stream_max_segments``, which no window of any order exceeds; a smaller one that a batch overflows
         gives that batch as padding with ``n_rows`` = -1). ``shuffle_rows``: the rows of an epoch in the order of
@@ -336,11 +367,12 @@ class ResidentTokenStreamLoader(TokenStreamLoader):
         are the same in every epoch, so ``total_tokens`` -- the tokens of one epoch, computed here once -- and
         with it the rows and batches per epoch and the checkpoint cursor are constants; the default
         ``max_segments`` is ``ops.stream_max_segments`` over the lengths with every document counted
-        ``mix.max_copies`` times, a multiset that holds every epoch's documents."""
+        ``mix.max_copies`` times, a multiset that holds every epoch's documents. ``fim``: a ``TokenFIM``, the
+        fill-in-the-middle rearrangement of a share of every batch's segments (the module's text)."""
         self._init_stream(source, global_batch, seq_len, env, seed=seed, shuffle=shuffle, pad_id=pad_id, depth=depth,
                           device=device, n_epochs=n_epochs, resume_state=resume_state, handoff=handoff,
                           max_segments=max_segments, labels=labels, ignore_index=ignore_index,
-                          shuffle_rows=shuffle_rows, mix=mix)
+                          shuffle_rows=shuffle_rows, mix=mix, fim=fim)
         if not self._attach_replica(hbm_fraction, chunk_bytes):
             return
         try:
@@ -363,7 +395,7 @@ class ResidentTokenStreamLoader(TokenStreamLoader):
                 "rows_per_epoch": self.order.n_samples, "max_segments": self.max_segments,
                 "tables_built": self.tables_built, "shuffle_rows": self.shuffle_rows,
                 "mix_parts": self.mix.parts if self.mix is not None else 0, "mix_documents": self.n_order,
-                "orders_built": self.orders_built}
+                "orders_built": self.orders_built, "fim": self.fim is not None}
 
     def close(self) -> None:
         self._close_stream()

@@ -25,6 +25,7 @@ HBM use does not scale with the corpus's tokens: ``stats()["hbm_bytes"]`` is
     8 * (2 * (n_order + 1) + token_stream_table_scratch(n_order) + (2 * n_order with a mix))      tables, orders
     + 8 * (n_documents + 1)                                                                        offsets
     + (depth + 1) * ops.stream_zerocopy_window_bytes(LB, S, max_segments, token_bytes, shuffle_rows)   windows
+                                                                      (+ 4 * LB * S each with ``fim``, 16-byte aligned)
 
 (the batches a caller holds are its own). The corpus must fit in host memory.
 """
@@ -36,6 +37,7 @@ import torch
 from .exceptions import DDLError
 from .models.tokens import SharedTokenSource
 from .ops.kernels import launch_stream_plan_rows_zerocopy, launch_stream_plan_zerocopy, stream_zerocopy_window_bytes
+from .token_fim import TokenFIM
 from .token_mix import TokenMix
 from .token_stream import TokenStreamLoader
 from .types import DDLEnv
@@ -53,7 +55,7 @@ class ZeroCopyTokenStreamLoader(TokenStreamLoader):
                  n_epochs: int | None = None, resume_state: dict | None = None, prefault: bool = True,
                  handoff: str = "host", chunk_bytes: int = 256 << 20, max_segments: int | None = None,
                  labels: bool = False, ignore_index: int = -100, shuffle_rows: bool = False,
-                 mix: TokenMix | None = None):
+                 mix: TokenMix | None = None, fim: TokenFIM | None = None):
         """``ResidentTokenStreamLoader``'s arguments without ``hbm_fraction`` (no token is kept in HBM;
         ``chunk_bytes`` is accepted and unused, so that a call site can switch loaders), with ``max_blocks`` (the
         cap of the gather's grid, 0: none) and ``prefault`` (touch every page of the mapping once before the first
@@ -64,7 +66,7 @@ class ZeroCopyTokenStreamLoader(TokenStreamLoader):
         self._init_stream(source, global_batch, seq_len, env, seed=seed, shuffle=shuffle, pad_id=pad_id, depth=depth,
                           device=device, n_epochs=n_epochs, resume_state=resume_state, handoff=handoff,
                           max_segments=max_segments, labels=labels, ignore_index=ignore_index,
-                          shuffle_rows=shuffle_rows, mix=mix)
+                          shuffle_rows=shuffle_rows, mix=mix, fim=fim)
         if max_blocks is None:
             # swept once (profiles/zerocopy_stream/sweep_max_blocks.jsonl): 0 / 32 / 64 workgroups deliver
             # 2.61-2.81G / 2.12G / 2.63G tokens/s at 64 rows per step and 15.85-16.22G / 13.36G / 15.55G at 2048 --
@@ -98,7 +100,7 @@ class ZeroCopyTokenStreamLoader(TokenStreamLoader):
 
     def _window_bytes(self) -> int:
         return stream_zerocopy_window_bytes(self.LB, self.seq_len, self.max_segments, self.source.token_bytes,
-                                            self.shuffle_rows)
+                                            self.shuffle_rows) + self._fim_bytes
 
     @property
     def hbm_bytes(self) -> int:
@@ -114,7 +116,7 @@ class ZeroCopyTokenStreamLoader(TokenStreamLoader):
                 "format": "stream", "hbm_bytes": self.hbm_bytes, "rows_per_epoch": self.order.n_samples,
                 "max_segments": self.max_segments, "tables_built": self.tables_built,
                 "shuffle_rows": self.shuffle_rows, "mix_parts": self.mix.parts if self.mix is not None else 0,
-                "mix_documents": self.n_order, "orders_built": self.orders_built}
+                "mix_documents": self.n_order, "orders_built": self.orders_built, "fim": self.fim is not None}
 
     def close(self) -> None:
         self._close_stream()

@@ -43,6 +43,9 @@ stream by a second permutation, so the pieces of a long document no longer sit i
 ``--mix 2,1,0.5`` weights parts of the corpus (``ddl_amd.TokenMix``): the documents are cut into as many equal
 parts as there are numbers, and a document of part ``p`` appears ``repeat[p]`` times per epoch (a fraction: that
 share of the part's documents once more, the same ones every epoch).
+``--fim 0.5`` rearranges that share of the segments for fill-in-the-middle training (``ddl_amd.TokenFIM``, by a
+kernel behind the emit launch): ``<PRE> prefix <SUF> suffix <MID> middle`` or its SPM form, with the three sentinel
+ids just past the vocabulary; labels follow the rearranged ids.
 
 ``--zero-copy --stream`` delivers the same format from a corpus that stays in host memory
 (``ZeroCopyTokenStreamLoader``): only the offsets are uploaded, each batch's pieces are read over PCIe by
@@ -91,6 +94,8 @@ def main() -> None:
                     help="with --stream: the epoch's rows in a shuffled order (shuffle_rows=True)")
     ap.add_argument("--mix", default=None, metavar="R0,R1,...",
                     help="with --stream: repeats of equal parts of the corpus, e.g. 2,1,0.5 (TokenMix)")
+    ap.add_argument("--fim", type=float, default=None, metavar="RATE",
+                    help="with --stream: the share of segments rearranged for fill-in-the-middle (TokenFIM)")
     ap.add_argument("--labels", action="store_true",
                     help="with --resident or --zero-copy: the loader also delivers next-token labels, and every "
                          "batch runs a tiny embedding -> linear -> cross_entropy step on them")
@@ -111,6 +116,8 @@ def main() -> None:
         ap.error("--shuffle-rows is an option of --stream")
     if a.mix and not a.stream:
         ap.error("--mix is an option of --stream")
+    if a.fim is not None and not a.stream:
+        ap.error("--fim is an option of --stream")
     if a.labels and not (a.zero_copy or a.resident):
         ap.error("--labels needs --resident or --zero-copy (the producer path does not deliver labels)")
     vocab = a.vocab or (512 if a.labels else 50257)
@@ -136,9 +143,12 @@ def main() -> None:
                     repeat = [float(r) for r in a.mix.split(",")]
                     bounds = [round(p * a.n_seqs / len(repeat)) for p in range(len(repeat) + 1)]
                     mix = ddl_amd.TokenMix(bounds, repeat)
+                fim = None
+                if a.fim is not None:  # the sentinels just past the vocabulary
+                    fim = ddl_amd.TokenFIM(a.fim, prefix_id=vocab, middle_id=vocab + 1, suffix_id=vocab + 2)
                 stream_cls = ddl_amd.ResidentTokenStreamLoader if a.resident else ddl_amd.ZeroCopyTokenStreamLoader
                 dl = stream_cls(src, a.global_batch, a.seq_len, env, n_epochs=a.epochs, shuffle_rows=a.shuffle_rows,
-                                mix=mix, **lab_kw)
+                                mix=mix, fim=fim, **lab_kw)
                 if mix is not None and env.rank == 0:
                     print(f"mix: {mix.parts} parts x {list(mix.repeat)} -> {mix.n_order} documents and "
                           f"{dl.total_tokens} tokens per epoch (the corpus: {a.n_seqs} documents)", flush=True)
@@ -160,16 +170,22 @@ def main() -> None:
                                                    output=ddl_amd.OutputSpec(collate="tokens"), auto_mark=True)
             if a.labels:  # a toy causal-LM step: the loader's labels are what cross_entropy takes, as they come
                 torch.manual_seed(0)
-                model = torch.nn.Sequential(torch.nn.Embedding(vocab, 32), torch.nn.Linear(32, vocab)).to(dl.device)
+                n_ids = vocab + (3 if a.fim is not None else 0)  # the FIM sentinels are ids of their own
+                model = torch.nn.Sequential(torch.nn.Embedding(n_ids, 32), torch.nn.Linear(32, n_ids)).to(dl.device)
                 opt = torch.optim.SGD(model.parameters(), lr=0.1)
             for epoch in range(a.epochs):
                 real = rows = 0
-                for b in dl:
+                for step, b in enumerate(dl):
+                    if a.fim is not None and epoch == 0 and step == 0 and env.rank == 0:
+                        first = (b["position_ids"] == 0) & (b["attention_mask"] != 0)  # every segment's first token
+                        moved = int((b["input_ids"][first] == vocab).sum())
+                        print(f"fim: {moved} of {int(first.sum())} segments rearranged in the first batch "
+                              f"({100.0 * moved / max(int(first.sum()), 1):.1f}%, rate {a.fim})", flush=True)
                     real += int(b["attention_mask"].sum())
                     rows += int(b.get("n_rows", b["input_ids"].shape[0]))  # fixed rows: the packed ones
                     if a.labels:
                         logits = model(b["input_ids"])
-                        loss = torch.nn.functional.cross_entropy(logits.view(-1, vocab), b["labels"].view(-1),
+                        loss = torch.nn.functional.cross_entropy(logits.view(-1, n_ids), b["labels"].view(-1),
                                                                  ignore_index=-100)
                         opt.zero_grad(set_to_none=True)
                         loss.backward()
